@@ -670,36 +670,78 @@ __global__ __launch_bounds__(kThreads) void k_fill_gaps(const Gap *__restrict__ 
   }
 }
 
+// one compact directory group (common.h, dirc_entry) from its eight entries
+__device__ __forceinline__ uint2 dirc_group(const uint32_t (&t)[8], size_t g) {
+  uint32_t steps = 0;
+  bool esc = false;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const uint32_t d = t[i + 1] - t[i];
+    esc |= t[i + 1] < t[i] || d > 15u;
+    steps |= (d & 15u) << (4 * i);
+  }
+  return make_uint2(t[0], esc ? kDircEscape | (uint32_t)g : steps);
+}
+
 // largest number of slots any directory cell holds: max over e of table[e + 1] - table[e] (a segment's entries end with
 // its last slot + 1, which is where the next segment's begin: the difference across a boundary is 0). Also writes the
-// directory's three spare entries (query lanes read entries four at a time).
+// directory's three spare entries (query lanes read entries four at a time) and, from the same reads, its compact form.
 __global__ __launch_bounds__(kThreads) void k_max_cell(uint32_t *__restrict__ table, size_t nentries,
-                                                       uint32_t *__restrict__ out) {
+                                                       uint32_t *__restrict__ out, uint2 *__restrict__ dirc) {
   uint32_t m = 0;
   auto diff = [](uint32_t a, uint32_t b) { return b > a ? b - a : 0u; };
-  // four entries per 16-byte load and the one behind them (its line is the next group's), two groups in flight per thread
-  // (one entry and its neighbour per trip: 18 us for the 24 MB of config 3's directory)
-  const size_t n4 = nentries ? (nentries - 1) / 4 : 0;  // groups g whose entries 4g .. 4g + 4 all exist
+  // one group of eight entries (two 16-byte loads) and the entry behind it per trip, two groups in flight per thread
+  auto group = [&](const uint4 v, const uint4 w, uint32_t nx, size_t g) {
+    const uint32_t t[8] = {v.x, v.y, v.z, v.w, w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int i = 0; i < 7; ++i) m = max(m, diff(t[i], t[i + 1]));
+    m = max(m, diff(t[7], nx));
+    dirc[g] = dirc_group(t, g);
+  };
+  const size_t n8 = nentries ? (nentries - 1) / 8 : 0;  // groups g whose entries 8g .. 8g + 8 all exist
   const uint4 *t4 = reinterpret_cast<const uint4 *>(table);
   const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < n4; g += 2 * stride) {
+  for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < n8; g += 2 * stride) {
     const size_t g2 = g + stride;
-    const bool two = g2 < n4;
-    const uint4 v = t4[g];
-    const uint32_t nx = table[4 * g + 4];
-    uint4 w = make_uint4(0u, 0u, 0u, 0u);
-    uint32_t nw = 0;
+    const bool two = g2 < n8;
+    const uint4 v = t4[2 * g], w = t4[2 * g + 1];
+    const uint32_t nx = table[8 * g + 8];
+    uint4 v2 = make_uint4(0u, 0u, 0u, 0u), w2 = v2;
+    uint32_t nx2 = 0;
     if (two) {
-      w = t4[g2];
-      nw = table[4 * g2 + 4];
+      v2 = t4[2 * g2];
+      w2 = t4[2 * g2 + 1];
+      nx2 = table[8 * g2 + 8];
     }
-    m = max(max(m, diff(v.x, v.y)), max(max(diff(v.y, v.z), diff(v.z, v.w)), diff(v.w, nx)));
-    if (two) m = max(max(m, diff(w.x, w.y)), max(max(diff(w.y, w.z), diff(w.z, w.w)), diff(w.w, nw)));
+    group(v, w, nx, g);
+    if (two) group(v2, w2, nx2, g2);
   }
-  if (blockIdx.x == 0)
-    for (size_t i = 4 * n4 + threadIdx.x; i + 1 < nentries; i += kThreads) m = max(m, diff(table[i], table[i + 1]));
+  if (blockIdx.x == 0) {
+    for (size_t i = 8 * n8 + threadIdx.x; i + 1 < nentries; i += kThreads) m = max(m, diff(table[i], table[i + 1]));
+    // the last group or two (entries past the directory's end repeat its last: such a group is never probed beyond it)
+    const size_t g = n8 + threadIdx.x;
+    if (g < dirc_groups(nentries)) {
+      uint32_t t[8];
+      t[0] = table[8 * g];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) t[i] = 8 * g + i < nentries ? table[8 * g + i] : t[i - 1];
+      dirc[g] = dirc_group(t, g);
+    }
+  }
   if (blockIdx.x == 0 && threadIdx.x < 3) table[nentries + threadIdx.x] = 0xFFFFFFFFu;
   block_max_to(m, out);
+}
+
+// test hook (bivx_test_check_dirc): out[0] += entries whose compact form decodes to anything but table[e], out[1] += escaped
+// groups
+__global__ __launch_bounds__(kThreads) void k_check_dirc(const uint32_t *__restrict__ table, const uint2 *__restrict__ dirc,
+                                                         size_t nentries, unsigned long long *__restrict__ out) {
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < nentries; e += (size_t)gridDim.x * kThreads) {
+    const uint2 g = dirc[e >> kDircShift];
+    const uint32_t k = (uint32_t)e & ((1u << kDircShift) - 1u);
+    if (dirc_entry(g, k, table) != table[e]) atomicAdd(&out[0], 1ull);
+    if (k == 0 && (g.y & kDircEscape)) atomicAdd(&out[1], 1ull);
+  }
 }
 
 // The index's own intervals as a batch of queries in slot order (bivx_self_overlaps_dev): (chromosome of the slot's
@@ -868,8 +910,8 @@ size_t finalize_gap_bytes(uint64_t nentries, uint32_t nseg) { return finalize_ga
 
 int launch_finalize(const uint32_t *d_keys, const uint32_t *d_ids, const uint32_t *d_low, const uint32_t *d_high,
                     const SegDesc *d_seg, const uint2 *d_segkey, uint32_t nseg, uint2 *d_se, uint2 *d_rec,
-                    uint32_t *d_table, uint64_t nentries, void *d_gaps, uint32_t *d_ngaps, uint32_t *d_max_cell,
-                    size_t n, hipStream_t s) {
+                    uint32_t *d_table, uint2 *d_dirc, uint64_t nentries, void *d_gaps, uint32_t *d_ngaps,
+                    uint32_t *d_max_cell, size_t n, hipStream_t s) {
   if (n == 0 || nseg == 0) return 0;
   const uint32_t nchunks = grid_for(n, kThreads * kFinSlots);
   const unsigned grid = ((nchunks + 7u) / 8u) * 8u;
@@ -882,8 +924,16 @@ int launch_finalize(const uint32_t *d_keys, const uint32_t *d_ids, const uint32_
     hipLaunchKernelGGL(k_finalize<false>, dim3(grid), dim3(kThreads), 0, s, d_keys, d_ids, d_low, d_high, d_seg, d_segkey,
                        nseg, d_se, d_rec, d_table, gaps, d_ngaps, cap, n, nchunks);
   hipLaunchKernelGGL(k_fill_gaps, dim3(256), dim3(kThreads), 0, s, gaps, d_ngaps, cap, d_table);
-  hipLaunchKernelGGL(k_max_cell, dim3(grid_for(nentries, kThreads * 8, 512)), dim3(kThreads), 0, s, d_table, (size_t)nentries,
-                     d_max_cell);
+  hipLaunchKernelGGL(k_max_cell, dim3(grid_for(nentries, kThreads * 16, 512)), dim3(kThreads), 0, s, d_table, (size_t)nentries,
+                     d_max_cell, d_dirc);
+  BIVX_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_check_dirc(const uint32_t *d_table, const uint2 *d_dirc, uint64_t nentries, uint64_t *d_out2, hipStream_t s) {
+  if (nentries == 0) return 0;
+  hipLaunchKernelGGL(k_check_dirc, dim3(grid_for(nentries, kThreads, 1024)), dim3(kThreads), 0, s, d_table, d_dirc,
+                     (size_t)nentries, reinterpret_cast<unsigned long long *>(d_out2));
   BIVX_HIP(hipGetLastError());
   return 0;
 }

@@ -80,6 +80,7 @@ struct bivx_index {
   uint2 *d_rec = nullptr;
   uint32_t *d_id = nullptr;
   uint32_t *d_table = nullptr;
+  uint2 *d_dirc = nullptr;             // the directory's compact form, behind the table in b_table
   SegDesc *d_seg = nullptr;
   uint2 *d_chrom_rng = nullptr;        // ntypes rows of nchrom (first segment, count) pairs; row 0 = every type
   uint32_t nchrom = 0, nseg = 0, ntypes = 1;
@@ -248,6 +249,7 @@ void free_built(bivx_index *idx) {
   idx->d_rec = nullptr;
   idx->d_id = nullptr;
   idx->d_table = nullptr;
+  idx->d_dirc = nullptr;
   idx->d_seg = nullptr;
   idx->d_chrom_rng = nullptr;
   idx->nchrom = idx->nseg = 0;
@@ -627,6 +629,7 @@ IndexView view_of(const bivx_index *idx, uint32_t svtype = 0) {
   v.rec = idx->d_rec;
   v.id = idx->d_id;
   v.table = idx->d_table;
+  v.dirc = idx->d_dirc;
   v.seg = idx->d_seg;
   // row of the requested interval type; a type the index does not hold selects an all-empty row
   const uint32_t row = svtype < idx->ntypes ? svtype : idx->ntypes;
@@ -1212,9 +1215,12 @@ int bivx_build(bivx_index *idx) {
     BIVX_TRY(ensure_block(idx->b_se, 2 * se_bytes));
     idx->d_se = static_cast<uint2 *>(idx->b_se.p);
     idx->d_rec = reinterpret_cast<uint2 *>(static_cast<char *>(idx->b_se.p) + se_bytes);
-    // 6. ... and the bucket directory, by the same pass (+3 spare entries: query lanes read entries four at a time)
-    BIVX_TRY(ensure_block(idx->b_table, ((size_t)plan.nentries + 3) * 4));
+    // 6. ... and the bucket directory, by the same pass (+3 spare entries: query lanes read entries four at a time), its
+    // compact form behind it
+    const size_t table_bytes = (((size_t)plan.nentries + 3) * 4 + 255) & ~(size_t)255;
+    BIVX_TRY(ensure_block(idx->b_table, table_bytes + dirc_groups(plan.nentries) * sizeof(uint2)));
     idx->d_table = static_cast<uint32_t *>(idx->b_table.p);
+    idx->d_dirc = reinterpret_cast<uint2 *>(static_cast<char *>(idx->b_table.p) + table_bytes);
     // The dense-key sort leaves out the key's low `skip` bits when the plan says that saves a radix pass
     // (ClassPlan::order_shift): the slots then come out ordered by directory cell, append order inside a cell.
     auto sort_and_finalize = [&](int skip) -> int {
@@ -1240,7 +1246,8 @@ int bivx_build(bivx_index *idx) {
       }
       idx->d_id = vA;  // (one of the two id blocks; it stays the index's until the next build)
       BIVX_TRY(launch_finalize(dense ? kA : nullptr, idx->d_id, idx->d_low, idx->d_high, idx->d_seg, d_segkey, nseg, idx->d_se,
-                               idx->d_rec, idx->d_table, plan.nentries, idx->b_radix.p, d_scalar + 3, d_scalar + 2, n, s));
+                               idx->d_rec, idx->d_table, idx->d_dirc, plan.nentries, idx->b_radix.p, d_scalar + 3, d_scalar + 2,
+                               n, s));
       BIVX_HIP(hipMemcpyAsync(idx->h_scalars + 2, d_scalar + 2, 4, hipMemcpyDeviceToHost, s));
       return 0;
     };
@@ -1581,6 +1588,38 @@ int bivx_debug_corrupt_workspace(const bivx_index *idx, void *stream) {
     return BIVX_E_STATE;
   }
   BIVX_HIP(hipMemsetAsync(it->second.p, 0x7F, sizeof(uint32_t), s));  // ticket word: far beyond any grid
+  return 0;
+}
+
+// Test hook, not part of bivx.h: decodes every entry of the built index's compact directory on the device and compares it
+// with the table. out[0] = entries that differ, out[1] = escaped groups, out[2] = groups.
+int bivx_test_check_dirc(const bivx_index *idx, uint64_t *out) {
+  if (!idx || !out) {
+    set_error("bivx_test_check_dirc: null argument");
+    return BIVX_E_INVALID;
+  }
+  BIVX_NOT_SHARDED(idx, "bivx_test_check_dirc");
+  if (!idx->built) {
+    set_error("bivx_test_check_dirc: index not built");
+    return BIVX_E_STATE;
+  }
+  BIVX_GUARD(idx);
+  BIVX_HIP(hipStreamSynchronize(idx->stream));
+  uint64_t *d = nullptr;
+  BIVX_HIP(hipMalloc(&d, 2 * sizeof(uint64_t)));
+  uint64_t h[2] = {0, 0};
+  int rc = hipMemsetAsync(d, 0, 2 * sizeof(uint64_t), idx->stream) == hipSuccess ? 0 : BIVX_E_HIP;
+  if (rc == 0 && idx->built_n) rc = launch_check_dirc(idx->d_table, idx->d_dirc, idx->nentries, d, idx->stream);
+  if (rc == 0 && hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, idx->stream) != hipSuccess) rc = BIVX_E_HIP;
+  if (rc == 0 && hipStreamSynchronize(idx->stream) != hipSuccess) rc = BIVX_E_HIP;
+  (void)hipFree(d);
+  if (rc) {
+    set_error("bivx_test_check_dirc: device error");
+    return rc;
+  }
+  out[0] = h[0];
+  out[1] = h[1];
+  out[2] = idx->built_n ? dirc_groups(idx->nentries) : 0;
   return 0;
 }
 
@@ -2018,7 +2057,8 @@ int bivx_get_stats(const bivx_index *idx, bivx_stats *out) {
   out->n_cells = idx->nentries;
   out->staging_bytes = (uint64_t)idx->cap * 12;
   if (idx->built)
-    out->index_bytes = (uint64_t)idx->built_n * 20 + idx->nentries * 4 + (uint64_t)idx->nseg * sizeof(SegDesc) +
+    out->index_bytes = (uint64_t)idx->built_n * 20 + idx->nentries * 4 + dirc_groups(idx->nentries) * sizeof(uint2) +
+                       (uint64_t)idx->nseg * sizeof(SegDesc) +
                        ((uint64_t)idx->nchrom + 1) * 4;
   out->build_ms = idx->build_ms;
   {

@@ -51,6 +51,7 @@ struct IndexView {
   const uint2 *rec;           // packed (record, id) pairs (meaningful in kSegPacked segments only)
   const uint32_t *id;         // append-order id of each sorted slot
   const uint32_t *table;      // bucket directories, all segments back to back
+  const uint2 *dirc;          // the same directory in eight-entry groups (see dirc_entry): what k_query_pipe probes
   const SegDesc *seg;         // nseg descriptors, grouped by chromosome
   // segments of chromosome c as (first, count), for the interval type this call asks for: the index keeps one such
   // row per svtype (row 0: every type), so selecting a type costs the kernels nothing (bivx_filter::svtype)
@@ -74,6 +75,24 @@ struct IndexView {
   // the index's error block: host memory mapped into the device; kernels only ever store 1 into its words
   uint32_t *err;
 };
+
+// Compact directory: entry e of `table` lives in group e >> kDircShift, a uint2 of (table[8g], the seven steps
+// table[8g + i + 1] - table[8g + i], i = 0 .. 6, as 4-bit fields i). A quarter of the table's bytes, so that a chromosome's
+// directory stays in every L2 and leaves the space to the records. A group with a step that does not fit (a cell of more
+// than fifteen slots, a step down) is ESCAPED: .y = kDircEscape | g, and its entries are read from `table` itself.
+constexpr uint32_t kDircShift = 3;
+constexpr uint32_t kDircEscape = 1u << 31;
+__host__ __device__ inline size_t dirc_groups(uint64_t nentries) { return (size_t)((nentries + 7) >> kDircShift); }
+
+// table[8g + k] from its group word (k < 8): the base plus the masked nibble sum of the steps below k
+__device__ __forceinline__ uint32_t dirc_entry_plain(uint2 g, uint32_t k) {  // (a group known not to be escaped)
+  return g.x + __builtin_amdgcn_udot8(g.y & ((1u << (4u * k)) - 1u), 0x11111111u, 0u, false);
+}
+__device__ __forceinline__ uint32_t dirc_entry(uint2 g, uint32_t k, const uint32_t *table) {
+  if (g.y & kDircEscape) return table[((g.y & ~kDircEscape) << kDircShift) + k];
+  return dirc_entry_plain(g, k);
+}
+
 constexpr uint32_t kErrTimeout = 0;    // a bounded cross-workgroup wait of the single-pass kernel expired
 constexpr uint32_t kErrWorkspace = 1;  // the prefix workspace was not zero when a launch began
 constexpr uint32_t kErrWords = 16;     // size of the block (one cache line)
@@ -170,12 +189,15 @@ int radix_sort_pairs(uint32_t **keys, uint32_t **vals, uint32_t **keys_alt, uint
                      int nbits, void *d_scratch, bool vals_are_iota, bool hist0_ready, hipStream_t s, int first_shift = 0);
 // se[], rec[] and the bucket directory (with its three spare entries) from the sorted ids (and the sorted dense keys;
 // d_keys == nullptr: low is gathered by id). d_gaps: finalize_gap_bytes() of scratch; *d_ngaps and *d_max_cell must be
-// zero; *d_max_cell receives the largest number of slots any directory cell holds.
+// zero; *d_max_cell receives the largest number of slots any directory cell holds. d_dirc (dirc_groups(nentries) groups)
+// receives the directory's compact form.
 size_t finalize_gap_bytes(uint64_t nentries, uint32_t nseg);
 int launch_finalize(const uint32_t *d_keys, const uint32_t *d_ids, const uint32_t *d_low, const uint32_t *d_high,
                     const SegDesc *d_seg, const uint2 *d_segkey, uint32_t nseg, uint2 *d_se, uint2 *d_rec,
-                    uint32_t *d_table, uint64_t nentries, void *d_gaps, uint32_t *d_ngaps, uint32_t *d_max_cell,
-                    size_t n, hipStream_t s);
+                    uint32_t *d_table, uint2 *d_dirc, uint64_t nentries, void *d_gaps, uint32_t *d_ngaps,
+                    uint32_t *d_max_cell, size_t n, hipStream_t s);
+// d_out2[0] += directory entries whose compact form does not decode to the table's word, d_out2[1] += escaped groups
+int launch_check_dirc(const uint32_t *d_table, const uint2 *d_dirc, uint64_t nentries, uint64_t *d_out2, hipStream_t s);
 int launch_gather_intervals(const uint32_t *d_chrom, const uint32_t *d_low, const uint32_t *d_high,
                             const uint32_t *d_ids, size_t n, size_t n_intervals, uint32_t *d_c, uint32_t *d_l,
                             uint32_t *d_h, hipStream_t s);

@@ -177,6 +177,19 @@ struct Win {
   uint32_t fl;  // 1: the query reaches the segment.s cells (the window is non-empty if also b > a); 2: packed records decodable
 };
 
+// The same probe on its way (k_query_pipe): the compact directory groups (common.h, dirc_entry) of the window's two
+// entries, decoded into a Win when the window is used. fl as Win's, plus bits 2-4 / 5-7: the entries' places in their groups.
+struct WinProbe {
+  uint2 ga, gb;
+  uint32_t base, fl;
+};
+__device__ __forceinline__ Win win_of(const WinProbe &p, const uint32_t *table) {
+  const uint32_t ka = (p.fl >> 2) & 7u, kb = (p.fl >> 5) & 7u;
+  if ((p.ga.y | p.gb.y) & kDircEscape)  // (one test for both: escaped groups are rare)
+    return Win{dirc_entry(p.ga, ka, table), dirc_entry(p.gb, kb, table), p.base, p.fl & 3u};
+  return Win{dirc_entry_plain(p.ga, ka), dirc_entry_plain(p.gb, kb), p.base, p.fl & 3u};
+}
+
 // Hit mask of a window shorter than 32 slots, read by its own lane (queries in arbitrary order: the windows of a
 // wavefront are scattered over the index). The first sixteen slots — two chunks, up to eight 16-byte loads — leave
 // together, so a window that straddles two chunks costs one round trip, not two; a load is issued only by the lanes whose
@@ -711,11 +724,12 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
     return load_query<false>(w, cs, p->a.qchrom, p->a.qlow, p->a.qhigh, q, t < p->a.ntiles && q < p->a.q_end);
   };
 
-  // The bucket-directory probe of a query (seg_window's arithmetic, query_device.h), issued and NOT waited for: a and b
-  // are the two directory words on their way; `fl` says whether the query touches the segment's cells at all (1) and
-  // whether the window's packed records are decodable (2). The window is non-empty if fl & 1 and b > a.
+  // The bucket-directory probe of a query (seg_window's arithmetic, query_device.h), issued and NOT waited for: ga and gb
+  // are the compact directory groups of its two entries on their way (win_of decodes them); `fl` says whether the query
+  // touches the segment's cells at all (1) and whether the window's packed records are decodable (2). The window is
+  // non-empty if fl & 1 and b > a. (The compact form, not `table`: a chromosome's directory then stays in the L2s.)
   auto window_of = [&](const Query &q) {
-    Win w{0u, 0u, 0u, 0u};
+    WinProbe w{make_uint2(0u, 0u), make_uint2(0u, 0u), 0u, 0u};
     if (q.nseg) {
       const SegDesc d = load_seg(segs + q.s0);
       const uint32_t x = q.lo > d.maxlen ? q.lo - d.maxlen : 0u;
@@ -723,12 +737,14 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
         const uint32_t sh = d.shift & 31u;
         const uint32_t ca = x <= d.base ? 0u : (x - d.base) >> sh;
         const uint32_t cb = q.hi >= d.last ? d.ncell : ((q.hi - d.base) >> sh) + 1u;
-        // (32-bit byte offsets: the directory has fewer entries than the index has records, at most 2^28 here)
-        const char *t = reinterpret_cast<const char *>(fresh(ka)->v.table);
-        w.a = *reinterpret_cast<const uint32_t *>(t + ((d.table_off + ca) << 2));
-        w.b = *reinterpret_cast<const uint32_t *>(t + ((d.table_off + cb) << 2));
+        const uint32_t ea = d.table_off + ca, eb = d.table_off + cb;
+        // (32-bit byte offsets: group e >> 3 begins at byte e & ~7, and the directory has fewer than 2^32 entries)
+        const char *t = reinterpret_cast<const char *>(fresh(ka)->v.dirc);
+        w.ga = *reinterpret_cast<const uint2 *>(t + (ea & ~7u));
+        w.gb = *reinterpret_cast<const uint2 *>(t + (eb & ~7u));
         w.base = d.base + (ca << sh);
-        w.fl = 1u | ((d.shift & kSegPacked) != 0 && ((uint64_t)(cb - ca) << sh) <= 65536ull ? 2u : 0u);
+        w.fl = 1u | ((d.shift & kSegPacked) != 0 && ((uint64_t)(cb - ca) << sh) <= 65536ull ? 2u : 0u) | (ea & 7u) << 2 |
+               (eb & 7u) << 5;
       }
     }
     return w;
@@ -798,12 +814,12 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
   // probe, both issued an iteration ahead (the queries when the ticket comes in, the probe when they have arrived —
   // behind the flush — so that its round trip runs under the id layout).
   uint32_t qlo, qhi;
-  Win wn;
+  WinProbe wp;
   {
     const Query q0 = query_of(tile);
     qlo = q0.lo;
     qhi = q0.hi;
-    wn = window_of(q0);
+    wp = window_of(q0);
   }
   if (threadIdx.x == 0) { WGSTAMP(3); }
 
@@ -823,6 +839,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
       // index (a position-sorted batch): their union goes through the LDS slab once; (2) all short, scattered (or only
       // partly neighbours): every lane reads its own; (0) long windows, unpacked segments: the general enumeration
       // counts, and the slice's ids are k_fill_slices' business (it is listed like one that overflows its stage).
+      const Win wn = win_of(wp, fresh(ka)->v.table);
       const bool nonempty = (wn.fl & 1u) != 0 && wn.b > wn.a;
       const uint32_t al = wn.a & ~1u;
       qw_a = wn.a;
@@ -867,6 +884,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
         v1.rec = p->v.rec;
         v1.id = p->v.id;
         v1.table = p->v.table;
+        v1.dirc = p->v.dirc;
         v1.seg = nullptr;
         v1.chrom_rng = nullptr;
         v1.nchrom = 0;
@@ -901,7 +919,8 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
           if (lane >= d) i64 += o;
         }
         lpos64 = i64 - cnt;
-        wt64 = __shfl((unsigned long long)i64, kWave - 1, kWave);
+        // (read off the last lane: a shuffle's lane address, made once in front of the loop, would take a register)
+        wt64 = (uint64_t)wave_last((uint32_t)i64) | (uint64_t)wave_last((uint32_t)(i64 >> 32)) << 32;
       }
       // report the slice's total (the service wavefront publishes the tile when all fifteen are in)
       TileSlot &sl = s_slot[it % kRing];
@@ -936,7 +955,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
       break;
     }
     PSTAMP(tile, 3);
-    const Win nwn = window_of(nqy);  // (its two loads are consumed at the top of the next iteration)
+    const WinProbe nwp = window_of(nqy);  // (its two loads are consumed at the top of the next iteration)
 
     // ---- lay the new slice's ids out in the stage, back to back as they will sit in the output -------------------
 #pragma unroll
@@ -1037,7 +1056,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
     tile = ntile;
     qlo = nqy.lo;
     qhi = nqy.hi;
-    wn = nwn;
+    wp = nwp;
   }
 
 }
@@ -1286,6 +1305,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe_dense(IndexView v_i
         v1.rec = p->v.rec;
         v1.id = p->v.id;
         v1.table = p->v.table;
+        v1.dirc = p->v.dirc;
         v1.seg = nullptr;
         v1.chrom_rng = nullptr;
         v1.nchrom = 0;
@@ -1791,6 +1811,7 @@ __global__ __launch_bounds__(kMsThreads, BIVX_MS_WAVES) void k_query_pipe_ms(Ind
       v1.rec = p->v.rec;
       v1.id = p->v.id;
       v1.table = p->v.table;
+      v1.dirc = p->v.dirc;
       v1.seg = nullptr;
       v1.chrom_rng = nullptr;
       v1.nchrom = 0;
