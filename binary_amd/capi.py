@@ -20,7 +20,7 @@ EXPORTS = (
     "bivx_fill_dev", "bivx_query_workspace_bytes", "bivx_query_dev", "bivx_sort_hits_dev", "bivx_any", "bivx_any_dev", "bivx_get_stats",
     "bivx_count_f", "bivx_fill_f", "bivx_count_dev_f", "bivx_fill_dev_f", "bivx_query_dev_f", "bivx_query_dev_s", "bivx_query_dev_u",
     "bivx_find_overlaps", "bivx_free", "bivx_self_overlaps_dev", "bivx_stream_status", "bivx_query_kernel_name", "bivx_debug_corrupt_workspace", "bivx_release_pooled",
-    "bivx_query_sharded_dev",
+    "bivx_query_sharded_dev", "bivx_query_sharded_dev_q",
 )
 
 
@@ -116,6 +116,7 @@ def load() -> C.CDLL:
     L.bivx_self_overlaps_dev.argtypes = [vp, C.c_int, u64p, u32p, C.c_uint64, vp]
     L.bivx_query_dev_u.argtypes = [vp, u32p, u32p, u32p, sz, fp, u64p, u32p, u32p, C.c_uint64, u64p, vp, sz, vp]
     L.bivx_query_sharded_dev.argtypes = [vp, u32p, u32p, u32p, sz, C.c_int, C.POINTER(ShardedResult)]
+    L.bivx_query_sharded_dev_q.argtypes = [vp, u32p, u32p, u32p, sz, C.c_int, C.c_int, C.POINTER(ShardedResult), vp]
     if L.bivx_abi_version() >> 16 != ABI_VERSION >> 16:
         raise ImportError("libbivx.so ABI major version mismatch")
     _lib = L

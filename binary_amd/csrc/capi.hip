@@ -2041,6 +2041,22 @@ int bivx_query_sharded_dev(const bivx_index *idx, const uint32_t *qchrom, const 
   return sharded_query_dev(idx->sharded, qchrom, qlow, qhigh, q, sort_by_id, out);
 }
 
+int bivx_query_sharded_dev_q(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t *d_qlow,
+                             const uint32_t *d_qhigh, size_t q, int sort_by_id, int batch_order,
+                             bivx_sharded_result *out, void *stream) {
+  if (!idx || !out) {
+    set_error("bivx_query_sharded_dev_q: null argument");
+    return BIVX_E_INVALID;
+  }
+  if (!idx->sharded) {
+    set_error("bivx_query_sharded_dev_q: not a sharded handle (bivx_create_sharded); a single-device index answers "
+              "device-resident batches with bivx_query_dev_s");
+    return BIVX_E_STATE;
+  }
+  return sharded_query_dev_q(idx->sharded, d_qchrom, d_qlow, d_qhigh, q, sort_by_id, batch_order, out,
+                             static_cast<hipStream_t>(stream));
+}
+
 int bivx_get_stats(const bivx_index *idx, bivx_stats *out) {
   if (!idx || !out) {
     set_error("bivx_get_stats: null argument");

@@ -137,6 +137,25 @@ void sharded_stats(const ShardedState *st, bivx_stats *out);
 // the gathered device-resident CSR (bivx_query_sharded_dev)
 int sharded_query_dev(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                       size_t q, int sort_by_id, bivx_sharded_result *out);
+// the same for a device-resident batch (bivx_query_sharded_dev_q)
+int sharded_query_dev_q(const ShardedState *st, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
+                        size_t q, int sort_by_id, int batch_order, bivx_sharded_result *out, hipStream_t stream);
+
+// ---- route.hip: a device-resident batch split by shard, and a gathered CSR put back into batch order ----------------
+constexpr uint32_t kRouteMaxShards = 64;  // shard ids are ranked with six wavefront ballots
+// d_table[c]: the shard of chromosome c (ntab entries; a chromosome beyond the table goes to shard 0). Stable: shard s's
+// queries, in batch order, land as [chrom | low | high] columns of n_s words from word 3 d_disp[s] of d_out (3 q words);
+// d_query_of_row[d_disp[s] + j] is the batch index of the j-th; d_disp[0 .. k] (k + 1 words) is left on the device.
+size_t route_scratch_bytes(size_t q, uint32_t k);
+int route_queries(const uint8_t *d_table, uint32_t ntab, const uint32_t *d_qchrom, const uint32_t *d_qlow,
+                  const uint32_t *d_qhigh, size_t q, uint32_t k, uint32_t *d_out, uint32_t *d_query_of_row,
+                  uint64_t *d_disp, void *d_scratch, hipStream_t s);
+int launch_iota_u32(uint32_t *d_out, size_t n, hipStream_t s);
+// rows grouped in any order (row r answers query d_query_of_row[r], every query exactly one row) -> the canonical CSR of q
+// queries: d_off[q + 1], d_hits[d_row_off[q]]
+size_t batch_order_scratch_bytes(size_t q);
+int batch_order_csr(const uint64_t *d_row_off, const uint32_t *d_row_hits, const uint32_t *d_query_of_row, size_t q,
+                    uint64_t *d_off, uint32_t *d_hits, void *d_scratch, hipStream_t s);
 
 // ---- scan.hip ---------------------------------------------------------------------------------------
 // out[0..n] = exclusive prefix sums of in[0..n), out[n] = total. scratch: scan_scratch_bytes(n).

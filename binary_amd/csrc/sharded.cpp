@@ -53,6 +53,13 @@ struct ShardedState {
   mutable std::vector<ncclComm_t> comms;  // ncclCommInitAll over the handle's devices (all different), made on first use
   mutable bool comm_tried = false;
   mutable Buf out_off, out_hits, out_rows;  // the gathered CSR and its row -> query map, on devices[0]
+  // ---- bivx_query_sharded_dev_q: a device-resident batch routed on devices[0] (route.hip) ----------------------------
+  mutable Buf route_tab;                    // u8 chrom -> shard (a chromosome no device holds: shard 0)
+  mutable size_t route_tab_n = 0;           // entries of the uploaded table (0: not uploaded since the last build)
+  mutable Buf routed, route_scratch, route_disp;  // the shards' [chrom | low | high] blocks; counts and scan; k + 1 displacements
+  mutable Buf out_boff, out_bhits, order_scratch; // the gathered CSR in batch order, and the scratch that puts it there
+  mutable hipEvent_t in_ready = nullptr;    // the caller's stream -> the root's stream
+  mutable hipEvent_t routed_ev = nullptr;   // the root's stream (the blocks are routed) -> the other shards' streams
   mutable std::mutex dev_mutex;             // one gathered call at a time: the buffers above are the handle's
 };
 
@@ -243,6 +250,7 @@ static int clear_impl(ShardedState *st) {
   st->type.clear();
   st->typed = st->built = false;
   st->built_n = 0;
+  st->route_tab_n = 0;
   for (auto *p : st->shard) BIVX_TRY(bivx_clear(p));
   return 0;
 }
@@ -313,6 +321,7 @@ static int build_impl(ShardedState *st) {
   st->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (st->by_chrom) st->gid = std::move(ids);
   for (auto &d : st->dev) d.gid_n = 0;  // (the id tables uploaded for bivx_query_sharded_dev belong to the last build)
+  st->route_tab_n = 0;                   // (so does bivx_query_sharded_dev_q's chrom -> shard table)
   st->nchrom = nchrom;
   st->ntypes = st->typed ? max_type + 1 : 1;
   st->built = true;
@@ -532,6 +541,11 @@ int ensure_dev_state(const ShardedState *st) {
     }
     BIVX_HIP(hipStreamCreateWithFlags(&st->dev[s].stream, hipStreamNonBlocking));
   }
+  if (!st->in_ready || !st->routed_ev) {
+    OnDevice g(st->devices[0]);
+    if (!st->in_ready) BIVX_HIP(hipEventCreateWithFlags(&st->in_ready, hipEventDisableTiming));
+    if (!st->routed_ev) BIVX_HIP(hipEventCreateWithFlags(&st->routed_ev, hipEventDisableTiming));
+  }
   if (!st->comm_tried) {
     st->comm_tried = true;
     std::vector<int> d = st->devices;
@@ -547,6 +561,190 @@ int ensure_dev_state(const ShardedState *st) {
         return BIVX_E_COMM;
       }
     }
+  }
+  return 0;
+}
+
+}  // namespace
+
+namespace {
+
+// one shard's part of a gathered call: its queries in its own device's memory
+struct ShardIn {
+  const uint32_t *c = nullptr, *lo = nullptr, *hi = nullptr;  // c == nullptr: every query on chromosome 0
+  size_t m = 0;
+};
+
+// step 1 for shard s (on its device, its stream): count, size, single pass, ids made global; its CSR stays in d.off / d.hits
+int shard_answer(const ShardedState *st, size_t s, const ShardIn &in, int sort_by_id, uint64_t &nh) {
+  ShardedState::ShardDev &d = st->dev[s];
+  const size_t k = st->shard.size(), m = in.m;
+  BIVX_TRY(grow(d.sizes, 2 * sizeof(uint64_t) * (k + 1)));
+  BIVX_TRY(grow(d.off, (m + 1) * sizeof(uint64_t)));
+  if (m == 0) {
+    BIVX_HIP(hipMemsetAsync(d.off.p, 0, sizeof(uint64_t), d.stream));
+    BIVX_HIP(hipStreamSynchronize(d.stream));
+    return 0;
+  }
+  uint64_t *doff = static_cast<uint64_t *>(d.off.p);
+  BIVX_TRY(bivx_count_dev(st->shard[s], in.c, in.lo, in.hi, m, doff, d.stream));
+  uint64_t total = 0;
+  BIVX_HIP(hipMemcpyAsync(&total, doff + m, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+  BIVX_HIP(hipStreamSynchronize(d.stream));  // (also: the host vectors of a host sub-batch may go)
+  BIVX_TRY(bivx_stream_status(st->shard[s], d.stream));
+  nh = total;
+  if (total == 0) return 0;
+  BIVX_TRY(grow(d.hits, (size_t)total * sizeof(uint32_t)));
+  uint32_t *dh = static_cast<uint32_t *>(d.hits.p);
+  BIVX_TRY(bivx_query_dev_s(st->shard[s], in.c, in.lo, in.hi, m, nullptr, sort_by_id, doff, dh, total, nullptr, 0, d.stream));
+  if (st->by_chrom) {  // (shard-local ids ascend with the global ones: an ordered list stays ordered)
+    const auto &gl = st->gid[s];
+    if (d.gid_n != gl.size() || !d.gid.p) {
+      BIVX_TRY(grow(d.gid, gl.size() * sizeof(uint32_t)));
+      BIVX_HIP(hipMemcpyAsync(d.gid.p, gl.data(), gl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+      d.gid_n = gl.size();
+    }
+    hipLaunchKernelGGL(k_map_ids, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d.stream, dh, total,
+                       static_cast<const uint32_t *>(d.gid.p));
+    BIVX_HIP(hipGetLastError());
+  }
+  BIVX_HIP(hipStreamSynchronize(d.stream));
+  return bivx_stream_status(st->shard[s], d.stream);
+}
+
+struct Gathered {
+  uint64_t rows = 0, total = 0;
+  uint64_t *off = nullptr;
+  uint32_t *hits = nullptr;
+  bool rccl = false;
+  std::vector<uint64_t> disp;  // (the host side of an upload on the root's stream: kept until finish_gather)
+};
+
+// steps 2 - 4: the shards' CSRs (nq[s] rows, nh[s] ids each) gathered into devices[0]'s memory, rows grouped by device; the
+// work is left on the root's stream (finish_gather waits for it). The caller is on devices[0].
+int gather_blocks(const ShardedState *st, const std::vector<uint64_t> &nq, const std::vector<uint64_t> &nh, Gathered &g) {
+  const size_t k = st->shard.size();
+  // 2. sizes: ncclAllGather of (queries, ids) per device — every device learns every block's size, as a consumer on
+  // any device would need them; the host's copy of the same numbers drives the displacements below
+  const bool rccl = !st->comms.empty();
+  std::vector<uint64_t> qdisp(k + 1, 0), hdisp(k + 1, 0);
+  for (size_t s = 0; s < k; ++s) {
+    qdisp[s + 1] = qdisp[s] + nq[s];
+    hdisp[s + 1] = hdisp[s] + nh[s];
+  }
+  const uint64_t rows = qdisp[k], total = hdisp[k];
+  if (rccl) {
+    for (size_t s = 0; s < k; ++s) {
+      OnDevice gd(st->devices[s]);
+      const uint64_t mine[2] = {nq[s], nh[s]};
+      BIVX_HIP(hipMemcpyAsync(st->dev[s].sizes.p, mine, sizeof(mine), hipMemcpyHostToDevice, st->dev[s].stream));
+      BIVX_HIP(hipStreamSynchronize(st->dev[s].stream));  // (`mine` is a stack array)
+    }
+    BIVX_NCCL(ncclGroupStart());
+    for (size_t s = 0; s < k; ++s) {
+      OnDevice gd(st->devices[s]);  // (a communicator's calls are made with its device current)
+      uint64_t *sz = static_cast<uint64_t *>(st->dev[s].sizes.p);
+      const ncclResult_t e = ncclAllGather(sz, sz + 2, 2, ncclUint64, st->comms[s], st->dev[s].stream);
+      if (e != ncclSuccess) {
+        (void)ncclGroupEnd();
+        set_error("ncclAllGather failed: %s", ncclGetErrorString(e));
+        return BIVX_E_COMM;
+      }
+    }
+    BIVX_NCCL(ncclGroupEnd());
+    std::vector<uint64_t> seen(2 * k);
+    {
+      OnDevice gd(st->devices[0]);
+      BIVX_HIP(hipMemcpyAsync(seen.data(), static_cast<uint64_t *>(st->dev[0].sizes.p) + 2, 2 * k * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, st->dev[0].stream));
+      BIVX_HIP(hipStreamSynchronize(st->dev[0].stream));
+    }
+    for (size_t s = 0; s < k; ++s)
+      if (seen[2 * s] != nq[s] || seen[2 * s + 1] != nh[s]) {
+        set_error("bivx_query_sharded_dev: the gathered sizes of device %d are (%llu, %llu), expected (%llu, %llu)",
+                  st->devices[s], (unsigned long long)seen[2 * s], (unsigned long long)seen[2 * s + 1],
+                  (unsigned long long)nq[s], (unsigned long long)nh[s]);
+        return BIVX_E_COMM;
+      }
+  }
+  // 3. the blocks travel to devices[0]: offsets (without their last entry) and ids of every shard, each peer over its own
+  // link, all inside ONE group; the root's own block is a local copy
+  hipStream_t rs = st->dev[0].stream;
+  BIVX_TRY(grow(st->out_off, (rows + 1) * sizeof(uint64_t) + 2 * (k + 1) * sizeof(uint64_t)));
+  BIVX_TRY(grow(st->out_hits, std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
+  BIVX_TRY(grow(st->out_rows, std::max<uint64_t>(rows, 1) * sizeof(uint32_t)));
+  uint64_t *o_off = static_cast<uint64_t *>(st->out_off.p);
+  uint32_t *o_hits = static_cast<uint32_t *>(st->out_hits.p);
+  uint64_t *o_disp = o_off + rows + 1;  // (qdisp | hdisp for the rebasing kernel, behind the offsets)
+  auto local_copy = [&](size_t s) -> int {
+    if (nq[s]) BIVX_HIP(hipMemcpyAsync(o_off + qdisp[s], st->dev[s].off.p, nq[s] * sizeof(uint64_t), hipMemcpyDeviceToDevice, rs));
+    if (nh[s]) BIVX_HIP(hipMemcpyAsync(o_hits + hdisp[s], st->dev[s].hits.p, nh[s] * sizeof(uint32_t), hipMemcpyDeviceToDevice, rs));
+    return 0;
+  };
+  BIVX_TRY(local_copy(0));
+  if (rccl && k > 1) {
+    BIVX_NCCL(ncclGroupStart());
+    ncclResult_t e = ncclSuccess;
+    for (size_t s = 1; s < k && e == ncclSuccess; ++s) {
+      if (nq[s]) e = ncclRecv(o_off + qdisp[s], nq[s], ncclUint64, (int)s, st->comms[0], rs);
+      if (e == ncclSuccess && nh[s]) e = ncclRecv(o_hits + hdisp[s], nh[s], ncclUint32, (int)s, st->comms[0], rs);
+      OnDevice gd(st->devices[s]);  // (the peer's sends with the peer's device current; the root's is restored behind them)
+      if (e == ncclSuccess && nq[s]) e = ncclSend(st->dev[s].off.p, nq[s], ncclUint64, 0, st->comms[s], st->dev[s].stream);
+      if (e == ncclSuccess && nh[s]) e = ncclSend(st->dev[s].hits.p, nh[s], ncclUint32, 0, st->comms[s], st->dev[s].stream);
+    }
+    if (e != ncclSuccess) {
+      (void)ncclGroupEnd();
+      set_error("ncclSend / ncclRecv failed: %s", ncclGetErrorString(e));
+      return BIVX_E_COMM;
+    }
+    BIVX_NCCL(ncclGroupEnd());
+  } else {
+    for (size_t s = 1; s < k; ++s) BIVX_TRY(local_copy(s));  // (shards that share the root's device: nothing to send)
+  }
+  // 4. offsets rebased to the gathered ids
+  std::vector<uint64_t> &disp = g.disp;
+  disp.resize(2 * (k + 1));
+  std::copy(qdisp.begin(), qdisp.end(), disp.begin());
+  std::copy(hdisp.begin(), hdisp.end(), disp.begin() + (k + 1));
+  BIVX_HIP(hipMemcpyAsync(o_disp, disp.data(), disp.size() * sizeof(uint64_t), hipMemcpyHostToDevice, rs));
+  hipLaunchKernelGGL(k_rebase_offsets, dim3((unsigned)((rows + 1 + 255) / 256)), dim3(256), 0, rs, o_off, o_disp, o_disp + (k + 1),
+                     (uint32_t)k, rows, total);
+  BIVX_HIP(hipGetLastError());
+  g.rows = rows;
+  g.total = total;
+  g.off = o_off;
+  g.hits = o_hits;
+  g.rccl = rccl;
+  return 0;
+}
+
+int finish_gather(const ShardedState *st) {
+  BIVX_HIP(hipStreamSynchronize(st->dev[0].stream));
+  for (size_t s = 1; s < st->shard.size(); ++s) {  // the peers' sends are complete when their streams are
+    OnDevice g(st->devices[s]);
+    BIVX_HIP(hipStreamSynchronize(st->dev[s].stream));
+  }
+  return 0;
+}
+
+void set_result(const ShardedState *st, const Gathered &g, bivx_sharded_result *out) {
+  out->d_offsets = g.off;
+  out->d_hit_ids = g.hits;
+  out->d_query_of_row = static_cast<uint32_t *>(st->out_rows.p);
+  out->rows = g.rows;
+  out->total = g.total;
+  out->device = st->devices[0];
+  out->used_rccl = g.rccl ? 1 : 0;
+}
+
+// a caller's column must lie in devices[0]'s memory
+int on_root_device(const ShardedState *st, const void *p, const char *name) {
+  hipPointerAttribute_t a{};
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  (void)hipGetLastError();  // (a host pointer fails the query: its error must not stay behind for the launches below)
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != st->devices[0]) {
+    set_error("bivx_query_sharded_dev_q: %s is not device memory of device %d", name, st->devices[0]);
+    return BIVX_E_INVALID;
   }
   return 0;
 }
@@ -582,7 +780,7 @@ static int query_dev_impl(const ShardedState *st, const uint32_t *qchrom, const 
       r.qs[0].swap(merged);
     }
   }
-  // 1. every shard answers its queries on its own device and stream: count, size, single pass, ids made global
+  // 1. every shard answers its queries on its own device and stream: its sub-batch gathered and uploaded, then shard_answer
   std::vector<uint64_t> nq(k, 0), nh(k, 0);
   BIVX_TRY(on_every_shard(st, [&](size_t s) -> int {
     ShardedState::ShardDev &d = st->dev[s];
@@ -593,154 +791,206 @@ static int query_dev_impl(const ShardedState *st, const uint32_t *qchrom, const 
     }
     const size_t m = r.qs[s].size();
     nq[s] = m;
-    BIVX_TRY(grow(d.sizes, 2 * sizeof(uint64_t) * (k + 1)));
-    BIVX_TRY(grow(d.off, (m + 1) * sizeof(uint64_t)));
-    if (m == 0) {
-      BIVX_HIP(hipMemsetAsync(d.off.p, 0, sizeof(uint64_t), d.stream));
-      BIVX_HIP(hipStreamSynchronize(d.stream));
-      return 0;
-    }
+    ShardIn in;
+    in.m = m;
     SubBatch b;
-    std::vector<uint32_t> iaux;
-    gather(st, s, r.qs[s], qchrom, qlow, qhigh, nullptr, b, iaux);
-    BIVX_TRY(grow(d.q, 3 * m * sizeof(uint32_t)));
-    uint32_t *dq = static_cast<uint32_t *>(d.q.p);
-    if (qchrom) BIVX_HIP(hipMemcpyAsync(dq, b.c.data(), m * 4, hipMemcpyHostToDevice, d.stream));
-    BIVX_HIP(hipMemcpyAsync(dq + m, b.lo.data(), m * 4, hipMemcpyHostToDevice, d.stream));
-    BIVX_HIP(hipMemcpyAsync(dq + 2 * m, b.hi.data(), m * 4, hipMemcpyHostToDevice, d.stream));
-    uint64_t *doff = static_cast<uint64_t *>(d.off.p);
-    BIVX_TRY(bivx_count_dev(st->shard[s], qchrom ? dq : nullptr, dq + m, dq + 2 * m, m, doff, d.stream));
-    uint64_t total = 0;
-    BIVX_HIP(hipMemcpyAsync(&total, doff + m, sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-    BIVX_HIP(hipStreamSynchronize(d.stream));  // (also: the host vectors of the sub-batch may go)
-    BIVX_TRY(bivx_stream_status(st->shard[s], d.stream));
-    nh[s] = total;
-    if (total == 0) return 0;
-    BIVX_TRY(grow(d.hits, (size_t)total * sizeof(uint32_t)));
-    uint32_t *dh = static_cast<uint32_t *>(d.hits.p);
-    BIVX_TRY(bivx_query_dev_s(st->shard[s], qchrom ? dq : nullptr, dq + m, dq + 2 * m, m, nullptr, sort_by_id, doff, dh, total,
-                              nullptr, 0, d.stream));
-    if (st->by_chrom) {  // (shard-local ids ascend with the global ones: an ordered list stays ordered)
-      const auto &gl = st->gid[s];
-      if (d.gid_n != gl.size() || !d.gid.p) {
-        BIVX_TRY(grow(d.gid, gl.size() * sizeof(uint32_t)));
-        BIVX_HIP(hipMemcpyAsync(d.gid.p, gl.data(), gl.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-        d.gid_n = gl.size();
-      }
-      hipLaunchKernelGGL(k_map_ids, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, d.stream, dh, total,
-                         static_cast<const uint32_t *>(d.gid.p));
-      BIVX_HIP(hipGetLastError());
+    if (m) {
+      std::vector<uint32_t> iaux;
+      gather(st, s, r.qs[s], qchrom, qlow, qhigh, nullptr, b, iaux);
+      BIVX_TRY(grow(d.q, 3 * m * sizeof(uint32_t)));
+      uint32_t *dq = static_cast<uint32_t *>(d.q.p);
+      if (qchrom) BIVX_HIP(hipMemcpyAsync(dq, b.c.data(), m * 4, hipMemcpyHostToDevice, d.stream));
+      BIVX_HIP(hipMemcpyAsync(dq + m, b.lo.data(), m * 4, hipMemcpyHostToDevice, d.stream));
+      BIVX_HIP(hipMemcpyAsync(dq + 2 * m, b.hi.data(), m * 4, hipMemcpyHostToDevice, d.stream));
+      in.c = qchrom ? dq : nullptr;
+      in.lo = dq + m;
+      in.hi = dq + 2 * m;
     }
-    BIVX_HIP(hipStreamSynchronize(d.stream));
-    return bivx_stream_status(st->shard[s], d.stream);
+    return shard_answer(st, s, in, sort_by_id, nh[s]);
   }));
-  // 2. sizes: ncclAllGather of (queries, ids) per device — every device learns every block's size, as a consumer on
-  // any device would need them; the host's copy of the same numbers drives the displacements below
-  const bool rccl = !st->comms.empty();
-  std::vector<uint64_t> qdisp(k + 1, 0), hdisp(k + 1, 0);
-  for (size_t s = 0; s < k; ++s) {
-    qdisp[s + 1] = qdisp[s] + nq[s];
-    hdisp[s + 1] = hdisp[s] + nh[s];
+  OnDevice root(st->devices[0]);
+  if (!root.ok) {
+    set_error("hipSetDevice(%d) failed", st->devices[0]);
+    return BIVX_E_HIP;
   }
-  const uint64_t rows = qdisp[k], total = hdisp[k];
-  if (rccl) {
-    for (size_t s = 0; s < k; ++s) {
-      OnDevice g(st->devices[s]);
-      const uint64_t mine[2] = {nq[s], nh[s]};
-      BIVX_HIP(hipMemcpyAsync(st->dev[s].sizes.p, mine, sizeof(mine), hipMemcpyHostToDevice, st->dev[s].stream));
-      BIVX_HIP(hipStreamSynchronize(st->dev[s].stream));  // (`mine` is a stack array)
-    }
-    BIVX_NCCL(ncclGroupStart());
-    for (size_t s = 0; s < k; ++s) {
-      OnDevice g(st->devices[s]);  // (a communicator's calls are made with its device current)
-      uint64_t *sz = static_cast<uint64_t *>(st->dev[s].sizes.p);
-      const ncclResult_t e = ncclAllGather(sz, sz + 2, 2, ncclUint64, st->comms[s], st->dev[s].stream);
-      if (e != ncclSuccess) {
-        (void)ncclGroupEnd();
-        set_error("ncclAllGather failed: %s", ncclGetErrorString(e));
-        return BIVX_E_COMM;
-      }
-    }
-    BIVX_NCCL(ncclGroupEnd());
-    std::vector<uint64_t> seen(2 * k);
-    {
-      OnDevice g(st->devices[0]);
-      BIVX_HIP(hipMemcpyAsync(seen.data(), static_cast<uint64_t *>(st->dev[0].sizes.p) + 2, 2 * k * sizeof(uint64_t),
-                              hipMemcpyDeviceToHost, st->dev[0].stream));
-      BIVX_HIP(hipStreamSynchronize(st->dev[0].stream));
-    }
-    for (size_t s = 0; s < k; ++s)
-      if (seen[2 * s] != nq[s] || seen[2 * s + 1] != nh[s]) {
-        set_error("bivx_query_sharded_dev: the gathered sizes of device %d are (%llu, %llu), expected (%llu, %llu)",
-                  st->devices[s], (unsigned long long)seen[2 * s], (unsigned long long)seen[2 * s + 1],
-                  (unsigned long long)nq[s], (unsigned long long)nh[s]);
-        return BIVX_E_COMM;
-      }
+  Gathered g;
+  BIVX_TRY(gather_blocks(st, nq, nh, g));
+  // the rows' batch indices
+  std::vector<uint32_t> row_q;
+  row_q.reserve(g.rows);
+  for (size_t s = 0; s < k; ++s) row_q.insert(row_q.end(), r.qs[s].begin(), r.qs[s].end());
+  if (g.rows)
+    BIVX_HIP(hipMemcpyAsync(st->out_rows.p, row_q.data(), g.rows * sizeof(uint32_t), hipMemcpyHostToDevice, st->dev[0].stream));
+  BIVX_TRY(finish_gather(st));
+  set_result(st, g, out);
+  return 0;
+}
+
+// The same for a batch already in devices[0]'s memory: routed by the kernels of route.hip on the root's stream, every
+// shard's block moved to its device (in place on devices[0], ncclSend / ncclRecv, or a peer copy), then steps 1 - 4 as
+// above; batch_order puts the gathered CSR back into batch order on the device.
+static int query_dev_q_impl(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
+                            size_t q, int sort_by_id, int batch_order, bivx_sharded_result *out, hipStream_t caller) {
+  if (!out || (q && (!qlow || !qhigh))) {
+    set_error("bivx_query_sharded_dev_q: null argument");
+    return BIVX_E_INVALID;
   }
-  // 3. the blocks travel to devices[0]: offsets (without their last entry) and ids of every shard, each peer over its own
-  // link, all inside ONE group; the root's own block is a local copy
+  std::memset(out, 0, sizeof(*out));
+  if (!sharded_is_built(st)) {
+    set_error("bivx_query_sharded_dev_q: index not built (call bivx_build after the last append)");
+    return BIVX_E_STATE;
+  }
+  const size_t k = st->shard.size();
+  if (q > 0xFFFFFFFFull) {
+    set_error("bivx_query_sharded_dev_q: more than 2^32 queries in one call");
+    return BIVX_E_RANGE;
+  }
+  if (k > kRouteMaxShards) {
+    set_error("bivx_query_sharded_dev_q: %zu devices, the routing kernel takes at most %u", k, kRouteMaxShards);
+    return BIVX_E_RANGE;
+  }
+  if (q) {
+    if (qchrom) BIVX_TRY(on_root_device(st, qchrom, "d_qchrom"));
+    BIVX_TRY(on_root_device(st, qlow, "d_qlow"));
+    BIVX_TRY(on_root_device(st, qhigh, "d_qhigh"));
+  }
+  std::lock_guard<std::mutex> lock(st->dev_mutex);
+  BIVX_TRY(ensure_dev_state(st));
   OnDevice root(st->devices[0]);
   if (!root.ok) {
     set_error("hipSetDevice(%d) failed", st->devices[0]);
     return BIVX_E_HIP;
   }
   hipStream_t rs = st->dev[0].stream;
-  BIVX_TRY(grow(st->out_off, (rows + 1) * sizeof(uint64_t) + 2 * (k + 1) * sizeof(uint64_t)));
-  BIVX_TRY(grow(st->out_hits, std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
-  BIVX_TRY(grow(st->out_rows, std::max<uint64_t>(rows, 1) * sizeof(uint32_t)));
-  uint64_t *o_off = static_cast<uint64_t *>(st->out_off.p);
-  uint32_t *o_hits = static_cast<uint32_t *>(st->out_hits.p);
-  uint64_t *o_disp = o_off + rows + 1;  // (qdisp | hdisp for the rebasing kernel, behind the offsets)
-  auto local_copy = [&](size_t s) -> int {
-    if (nq[s]) BIVX_HIP(hipMemcpyAsync(o_off + qdisp[s], st->dev[s].off.p, nq[s] * sizeof(uint64_t), hipMemcpyDeviceToDevice, rs));
-    if (nh[s]) BIVX_HIP(hipMemcpyAsync(o_hits + hdisp[s], st->dev[s].hits.p, nh[s] * sizeof(uint32_t), hipMemcpyDeviceToDevice, rs));
-    return 0;
+  // the columns are ready on the caller's stream: the root's stream waits for it (the caller's stream is not held up)
+  BIVX_HIP(hipEventRecord(st->in_ready, caller));
+  BIVX_HIP(hipStreamWaitEvent(rs, st->in_ready, 0));
+  // (the row map first: the routing writes it, and gather_blocks then finds it large enough)
+  BIVX_TRY(grow(st->out_rows, std::max<size_t>(q, 1) * sizeof(uint32_t)));
+  uint32_t *row_q = static_cast<uint32_t *>(st->out_rows.p);
+  // 0. every shard's block of the batch, in devices[0]'s memory
+  std::vector<ShardIn> in(k);
+  bool routed = false;
+  std::vector<uint8_t> tab;  // (a pageable upload reads it until the stream synchronise below)
+  if (!st->by_chrom) {       // replicated (one device included): contiguous ranges of the caller's columns
+    for (size_t s = 0; s < k; ++s) {
+      const size_t a = q * s / k, b = q * (s + 1) / k;
+      in[s] = ShardIn{qchrom ? qchrom + a : nullptr, qlow + a, qhigh + a, b - a};
+    }
+  } else if (!qchrom) {  // every query on chromosome 0: one shard answers the whole batch
+    const uint32_t s0 = !st->chrom_shard.empty() && st->chrom_shard[0] != 0xFFFFFFFFu ? st->chrom_shard[0] : 0u;
+    in[s0] = ShardIn{nullptr, qlow, qhigh, q};
+  } else {
+    routed = true;
+    const size_t ntab = st->chrom_shard.size();
+    if (st->route_tab_n != ntab || !st->route_tab.p) {
+      tab.resize(ntab);
+      for (size_t c = 0; c < ntab; ++c) tab[c] = st->chrom_shard[c] == 0xFFFFFFFFu ? 0 : (uint8_t)st->chrom_shard[c];
+      BIVX_TRY(grow(st->route_tab, ntab));
+      BIVX_HIP(hipMemcpyAsync(st->route_tab.p, tab.data(), ntab, hipMemcpyHostToDevice, rs));
+      st->route_tab_n = ntab;
+    }
+    BIVX_TRY(grow(st->routed, 3 * q * sizeof(uint32_t)));
+    BIVX_TRY(grow(st->route_scratch, route_scratch_bytes(q, (uint32_t)k)));
+    BIVX_TRY(grow(st->route_disp, (k + 1) * sizeof(uint64_t)));
+    uint32_t *blk = static_cast<uint32_t *>(st->routed.p);
+    BIVX_TRY(route_queries(static_cast<const uint8_t *>(st->route_tab.p), (uint32_t)ntab, qchrom, qlow, qhigh, q, (uint32_t)k,
+                           blk, row_q, static_cast<uint64_t *>(st->route_disp.p), st->route_scratch.p, rs));
+    std::vector<uint64_t> disp(k + 1);  // the one read-back of the call: the shards' sizes
+    BIVX_HIP(hipMemcpyAsync(disp.data(), st->route_disp.p, (k + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, rs));
+    BIVX_HIP(hipStreamSynchronize(rs));
+    for (size_t s = 0; s < k; ++s) {
+      const size_t m = (size_t)(disp[s + 1] - disp[s]);
+      const uint32_t *b = blk + 3 * disp[s];
+      in[s] = ShardIn{b, b + m, b + 2 * m, m};
+    }
+  }
+  const bool in_batch_order = routed ? in[0].m == q : true;  // (rows grouped by device are the batch's own order)
+  if (!batch_order && !routed) BIVX_TRY(launch_iota_u32(row_q, q, rs));
+  // the blocks of shards on other devices travel there: one group of ncclSend (root) / ncclRecv (peer), or peer copies
+  BIVX_HIP(hipEventRecord(st->routed_ev, rs));
+  const bool rccl = !st->comms.empty();
+  std::vector<size_t> far;
+  for (size_t s = 1; s < k; ++s) {
+    if (in[s].m == 0) continue;
+    if (st->devices[s] == st->devices[0]) {
+      BIVX_HIP(hipStreamWaitEvent(st->dev[s].stream, st->routed_ev, 0));  // (reads its block in place)
+      continue;
+    }
+    far.push_back(s);
+    OnDevice g(st->devices[s]);
+    BIVX_TRY(grow(st->dev[s].q, 3 * in[s].m * sizeof(uint32_t)));
+  }
+  auto columns = [&](size_t s, const uint32_t **src, uint32_t **dst) {
+    uint32_t *dq = static_cast<uint32_t *>(st->dev[s].q.p);
+    const size_t m = in[s].m;
+    src[0] = in[s].c, src[1] = in[s].lo, src[2] = in[s].hi;
+    dst[0] = dq, dst[1] = dq + m, dst[2] = dq + 2 * m;
   };
-  BIVX_TRY(local_copy(0));
-  if (rccl && k > 1) {
+  if (rccl && !far.empty()) {
     BIVX_NCCL(ncclGroupStart());
     ncclResult_t e = ncclSuccess;
-    for (size_t s = 1; s < k && e == ncclSuccess; ++s) {
-      if (nq[s]) e = ncclRecv(o_off + qdisp[s], nq[s], ncclUint64, (int)s, st->comms[0], rs);
-      if (e == ncclSuccess && nh[s]) e = ncclRecv(o_hits + hdisp[s], nh[s], ncclUint32, (int)s, st->comms[0], rs);
-      OnDevice g(st->devices[s]);  // (the peer's sends with the peer's device current; the root's is restored behind them)
-      if (e == ncclSuccess && nq[s]) e = ncclSend(st->dev[s].off.p, nq[s], ncclUint64, 0, st->comms[s], st->dev[s].stream);
-      if (e == ncclSuccess && nh[s]) e = ncclSend(st->dev[s].hits.p, nh[s], ncclUint32, 0, st->comms[s], st->dev[s].stream);
+    for (size_t s : far) {
+      const uint32_t *src[3];
+      uint32_t *dst[3];
+      columns(s, src, dst);
+      for (int j = 0; j < 3 && e == ncclSuccess; ++j)
+        if (src[j]) e = ncclSend(src[j], in[s].m, ncclUint32, (int)s, st->comms[0], rs);
+      OnDevice g(st->devices[s]);  // (the peer's receives with the peer's device current)
+      for (int j = 0; j < 3 && e == ncclSuccess; ++j)
+        if (src[j]) e = ncclRecv(dst[j], in[s].m, ncclUint32, 0, st->comms[s], st->dev[s].stream);
+      if (e != ncclSuccess) break;
     }
     if (e != ncclSuccess) {
       (void)ncclGroupEnd();
-      set_error("ncclSend / ncclRecv failed: %s", ncclGetErrorString(e));
+      set_error("ncclSend / ncclRecv of the queries failed: %s", ncclGetErrorString(e));
       return BIVX_E_COMM;
     }
     BIVX_NCCL(ncclGroupEnd());
   } else {
-    for (size_t s = 1; s < k; ++s) BIVX_TRY(local_copy(s));  // (shards that share the root's device: nothing to send)
+    for (size_t s : far) {
+      const uint32_t *src[3];
+      uint32_t *dst[3];
+      columns(s, src, dst);
+      OnDevice g(st->devices[s]);
+      BIVX_HIP(hipStreamWaitEvent(st->dev[s].stream, st->routed_ev, 0));
+      for (int j = 0; j < 3; ++j)
+        if (src[j])
+          BIVX_HIP(hipMemcpyPeerAsync(dst[j], st->devices[s], src[j], st->devices[0], in[s].m * sizeof(uint32_t), st->dev[s].stream));
+    }
   }
-  // 4. offsets rebased to the gathered ids, the rows' batch indices
-  std::vector<uint64_t> disp(2 * (k + 1));
-  std::copy(qdisp.begin(), qdisp.end(), disp.begin());
-  std::copy(hdisp.begin(), hdisp.end(), disp.begin() + (k + 1));
-  BIVX_HIP(hipMemcpyAsync(o_disp, disp.data(), disp.size() * sizeof(uint64_t), hipMemcpyHostToDevice, rs));
-  hipLaunchKernelGGL(k_rebase_offsets, dim3((unsigned)((rows + 1 + 255) / 256)), dim3(256), 0, rs, o_off, o_disp, o_disp + (k + 1),
-                     (uint32_t)k, rows, total);
-  BIVX_HIP(hipGetLastError());
-  std::vector<uint32_t> row_q;
-  row_q.reserve(rows);
-  for (size_t s = 0; s < k; ++s) row_q.insert(row_q.end(), r.qs[s].begin(), r.qs[s].end());
-  if (rows) BIVX_HIP(hipMemcpyAsync(st->out_rows.p, row_q.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice, rs));
-  BIVX_HIP(hipStreamSynchronize(rs));
-  for (size_t s = 1; s < k; ++s) {  // the peers' sends are complete when their streams are
+  for (size_t s : far) {
+    const uint32_t *src[3];
+    uint32_t *dst[3];
+    columns(s, src, dst);
+    in[s] = ShardIn{src[0] ? dst[0] : nullptr, dst[1], dst[2], in[s].m};
+  }
+  // 1. - 4. as for host-array queries
+  std::vector<uint64_t> nq(k, 0), nh(k, 0);
+  for (size_t s = 0; s < k; ++s) nq[s] = in[s].m;
+  BIVX_TRY(on_every_shard(st, [&](size_t s) -> int {
     OnDevice g(st->devices[s]);
-    BIVX_HIP(hipStreamSynchronize(st->dev[s].stream));
+    if (!g.ok) {
+      set_error("hipSetDevice(%d) failed", st->devices[s]);
+      return BIVX_E_HIP;
+    }
+    return shard_answer(st, s, in[s], sort_by_id, nh[s]);
+  }));
+  Gathered g;
+  BIVX_TRY(gather_blocks(st, nq, nh, g));
+  set_result(st, g, out);
+  if (batch_order) {
+    out->d_query_of_row = nullptr;
+    if (!in_batch_order) {  // (k > 1 by chromosome, queries beyond shard 0: the rows are a permutation of the batch)
+      BIVX_TRY(grow(st->out_boff, (q + 1) * sizeof(uint64_t)));
+      BIVX_TRY(grow(st->out_bhits, std::max<uint64_t>(g.total, 1) * sizeof(uint32_t)));
+      BIVX_TRY(grow(st->order_scratch, batch_order_scratch_bytes(q)));
+      out->d_offsets = static_cast<uint64_t *>(st->out_boff.p);
+      out->d_hit_ids = static_cast<uint32_t *>(st->out_bhits.p);
+      BIVX_TRY(batch_order_csr(g.off, g.hits, row_q, q, out->d_offsets, out->d_hit_ids, st->order_scratch.p, rs));
+    }
   }
-  out->d_offsets = o_off;
-  out->d_hit_ids = o_hits;
-  out->d_query_of_row = static_cast<uint32_t *>(st->out_rows.p);
-  out->rows = rows;
-  out->total = total;
-  out->device = st->devices[0];
-  out->used_rccl = rccl ? 1 : 0;
-  return 0;
+  return finish_gather(st);
 }
 
 static void release_dev_state(ShardedState *st) {
@@ -757,10 +1007,16 @@ static void release_dev_state(ShardedState *st) {
   st->dev.clear();
   if (!st->devices.empty()) {
     OnDevice g(st->devices[0]);
-    for (ShardedState::Buf *b : {&st->out_off, &st->out_hits, &st->out_rows}) {
+    for (ShardedState::Buf *b : {&st->out_off, &st->out_hits, &st->out_rows, &st->route_tab, &st->routed, &st->route_scratch,
+                                 &st->route_disp, &st->out_boff, &st->out_bhits, &st->order_scratch}) {
       (void)hipFree(b->p);
       b->p = nullptr;
       b->cap = 0;
+    }
+    st->route_tab_n = 0;
+    for (hipEvent_t *e : {&st->in_ready, &st->routed_ev}) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
     }
   }
 }
@@ -832,6 +1088,12 @@ int sharded_any(const ShardedState *st, const uint32_t *qchrom, const uint32_t *
 int sharded_query_dev(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                       size_t q, int sort_by_id, bivx_sharded_result *out) {
   return no_throw("bivx_query_sharded_dev", [&] { return query_dev_impl(st, qchrom, qlow, qhigh, q, sort_by_id, out); });
+}
+int sharded_query_dev_q(const ShardedState *st, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
+                        size_t q, int sort_by_id, int batch_order, bivx_sharded_result *out, hipStream_t stream) {
+  return no_throw("bivx_query_sharded_dev_q", [&] {
+    return query_dev_q_impl(st, d_qchrom, d_qlow, d_qhigh, q, sort_by_id, batch_order, out, stream);
+  });
 }
 
 }  // namespace bivx

@@ -45,12 +45,34 @@ def _check_dev_tensor(t, name, n=None, itemsize=4):
         raise ValueError(f"{name}: expected {n} elements, got {t.numel()}")
 
 
+def _take_sharded_result(res):
+    """(offsets int64[rows + 1], hit ids int32[total], query_of_row int32[rows] or None, used_rccl): torch tensors on
+    res.device COPIED out of the handle's buffers (which the next gathered call reuses)."""
+    dev = torch.device("cuda", res.device)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+
+    def take(ptr, n, dtype, itemsize):
+        t = torch.empty(n, dtype=dtype, device=dev)
+        if n:
+            with torch.cuda.device(dev):
+                rc = hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(ptr), n * itemsize, 3)  # device to device
+            if rc != 0:
+                raise RuntimeError(f"hipMemcpy of the gathered result failed: {rc}")
+        return t
+
+    off = take(res.d_offsets, res.rows + 1, torch.int64, 8)
+    hits = take(res.d_hit_ids, res.total, torch.int32, 4)
+    rows = take(res.d_query_of_row, res.rows, torch.int32, 4) if res.d_query_of_row else None
+    return off, hits, rows, bool(res.used_rccl)
+
+
 class IntervalIndex:
     """Batched drop-in for IntervalTree<UIntIntervalNode> (+ a chromosome id per interval/query)."""
 
     def __init__(self, device=0):
         """device: a HIP device ordinal, or a sequence of them for an index sharded by chromosome over several GPUs
-        of the node (bivx_create_sharded; host-array entry points only)."""
+        of the node (bivx_create_sharded; host-array entry points and the gathered query_sharded_device* calls)."""
         self._L = capi.load()
         h = C.c_void_p()
         if isinstance(device, (list, tuple)):
@@ -325,23 +347,23 @@ class IntervalIndex:
         res = capi.ShardedResult()
         capi.check(self._L.bivx_query_sharded_dev(self._h, _ptr(qchrom), _ptr(qlow), _ptr(qhigh), qlow.size, int(sort_by_id),
                                                   C.byref(res)))
-        dev = torch.device("cuda", res.device)
-        hip = C.CDLL("libamdhip64.so")
-        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        return _take_sharded_result(res)
 
-        def take(ptr, n, dtype, itemsize):
-            t = torch.empty(n, dtype=dtype, device=dev)
-            if n:
-                with torch.cuda.device(dev):
-                    rc = hip.hipMemcpy(C.c_void_p(t.data_ptr()), C.c_void_p(ptr), n * itemsize, 3)  # device to device
-                if rc != 0:
-                    raise RuntimeError(f"hipMemcpy of the gathered result failed: {rc}")
-            return t
-
-        off = take(res.d_offsets, res.rows + 1, torch.int64, 8)
-        hits = take(res.d_hit_ids, res.total, torch.int32, 4)
-        rows = take(res.d_query_of_row, res.rows, torch.int32, 4)
-        return off, hits, rows, bool(res.used_rccl)
+    def query_sharded_device_tensors(self, qlow, qhigh, qchrom=None, sort_by_id: bool = False, batch_order: bool = False):
+        """query_sharded_device for a batch already on the GPU (bivx_query_sharded_dev_q): qlow / qhigh / qchrom are 4-byte
+        device tensors on devices[0] (qchrom None: every query on chromosome 0), ready on the current stream; the queries are
+        routed to their chromosomes' devices by kernels on devices[0]. Returns copies as query_sharded_device does;
+        batch_order: the CSR in batch order (bivx_query_dev_s's, bit for bit with sort_by_id) and None for query_of_row."""
+        q = qlow.numel()
+        _check_dev_tensor(qlow, "qlow")
+        _check_dev_tensor(qhigh, "qhigh", q)
+        if qchrom is not None:
+            _check_dev_tensor(qchrom, "qchrom", q)
+        s = C.c_void_p(torch.cuda.current_stream(qlow.device).cuda_stream)
+        res = capi.ShardedResult()
+        capi.check(self._L.bivx_query_sharded_dev_q(self._h, _tptr(qchrom), _tptr(qlow), _tptr(qhigh), q, int(sort_by_id),
+                                                    int(batch_order), C.byref(res), s))
+        return _take_sharded_result(res)
 
     def find_overlaps_device(self, qlow, qhigh, qchrom=None, sort_by_id: bool = False):
         """(offsets int64[q+1], hits int32[H]) as device tensors. One host sync to size the hit buffer."""

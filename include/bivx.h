@@ -56,7 +56,8 @@ typedef enum bivx_status {
 #define BIVX_MAX_CHROMS 65536u
 #define BIVX_NO_HIT 0xFFFFFFFFu
 
-/* ABI version of this header: major << 16 | minor. */
+/* ABI version of this header: major << 16 | minor. (2.3 also carries bivx_query_sharded_dev_q; the minor goes up with the
+ * next change that moves the version's pin.) */
 #define BIVX_ABI_VERSION 0x00020003u
 uint32_t bivx_abi_version(void);
 const char *bivx_last_error(void);
@@ -113,6 +114,29 @@ typedef struct bivx_sharded_result {
 } bivx_sharded_result;
 int bivx_query_sharded_dev(const bivx_index *idx, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                            size_t q, int sort_by_id, bivx_sharded_result *out);
+/* The same batch with the QUERIES already in device memory: a sharded handle as a drop-in for bivx_query_dev_s.
+ * replaces: the reference's hand-off of each chromosome's records to the task that owns its tree (mapper.hpp:238-246) —
+ * here a stable partition of the batch by device, made by kernels on devices[0] (a per-tile count of the queries per
+ * device, one exclusive scan, a scatter ranked by wavefront ballots), instead of bivx_query_sharded_dev's host routing and
+ * pageable uploads. A device's block of queries is read in place when it is devices[0], travels in one
+ * ncclGroupStart .. ncclSend / ncclRecv .. ncclGroupEnd when the handle has a communicator, and by hipMemcpyPeerAsync
+ * otherwise; then the shards answer and their CSRs are gathered as above.
+ * d_qchrom / d_qlow / d_qhigh: device memory of devices[0] (d_qchrom may be NULL: every query on chromosome 0); `stream`: a
+ * hipStream_t of devices[0] on which they are ready (NULL: the default stream). The library's streams wait for it through an
+ * event; the call neither synchronises that stream nor the device, and returns when the result is complete (it reads the
+ * shards' sizes back to the host): it cannot be captured into a graph.
+ * batch_order == 0: exactly bivx_query_sharded_dev's result for the same queries in host memory (rows grouped by device,
+ * batch order inside a group, d_query_of_row; a query on a chromosome no device holds is answered, with no hit, by the
+ * first). batch_order != 0: rows == q, d_query_of_row == NULL, and d_offsets[q + 1] / d_hit_ids are the canonical CSR in
+ * batch order, put there on the device — with sort_by_id, bivx_query_dev_s's CSR of a single index bit for bit.
+ * Result buffers as above: the handle's, valid until the next bivx_query_sharded_dev*, bivx_build, bivx_clear or
+ * bivx_destroy. BIVX_E_STATE: a bivx_create handle, or one not built; BIVX_E_INVALID: a null out, null low / high columns
+ * with q > 0, or a column hipPointerGetAttributes does not place in devices[0]'s device memory (a host array);
+ * BIVX_E_RANGE: q >= 2^32, or a handle of more than 64 devices (the routing kernel ranks shard ids with six ballots);
+ * BIVX_E_COMM: a failed nccl* call. */
+int bivx_query_sharded_dev_q(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t *d_qlow,
+                             const uint32_t *d_qhigh, size_t q, int sort_by_id, int batch_order,
+                             bivx_sharded_result *out, void *stream);
 
 /* ---- build side -------------------------------------------------------------------------------
  * replaces: RbTree::insert_node(range) rb_tree.hpp:111-117 and insert_node(Args&&...) :145-149 — appends n
