@@ -20,7 +20,7 @@ EXPORTS = (
     "bivx_fill_dev", "bivx_query_workspace_bytes", "bivx_query_dev", "bivx_sort_hits_dev", "bivx_any", "bivx_any_dev", "bivx_get_stats",
     "bivx_count_f", "bivx_fill_f", "bivx_count_dev_f", "bivx_fill_dev_f", "bivx_query_dev_f", "bivx_query_dev_s", "bivx_query_dev_u",
     "bivx_find_overlaps", "bivx_free", "bivx_self_overlaps_dev", "bivx_stream_status", "bivx_query_kernel_name", "bivx_debug_corrupt_workspace", "bivx_release_pooled",
-    "bivx_query_sharded_dev", "bivx_query_sharded_dev_q",
+    "bivx_query_sharded_dev", "bivx_query_sharded_dev_q", "bivx_nearest", "bivx_nearest_dev",
 )
 
 
@@ -102,6 +102,8 @@ def load() -> C.CDLL:
     L.bivx_sort_hits_dev.argtypes = [vp, u64p, u32p, sz, vp]
     L.bivx_any.argtypes = [vp, u32p, u32p, u32p, sz, u32p]
     L.bivx_any_dev.argtypes = [vp, u32p, u32p, u32p, sz, u32p, vp]
+    L.bivx_nearest.argtypes = [vp, u32p, u32p, u32p, sz, C.c_uint32, C.c_uint32, u32p, u32p]
+    L.bivx_nearest_dev.argtypes = [vp, u32p, u32p, u32p, sz, C.c_uint32, C.c_uint32, u32p, u32p, vp]
     L.bivx_get_stats.argtypes = [vp, C.POINTER(Stats)]
     fp = C.POINTER(Filter)
     L.bivx_find_overlaps.argtypes = [vp, u32p, u32p, u32p, sz, fp, C.c_int, u64p, C.POINTER(C.POINTER(C.c_uint32))]

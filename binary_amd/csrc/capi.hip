@@ -1657,6 +1657,23 @@ int bivx_any_dev(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t
   return launch_any(view_of(idx), d_qchrom, d_qlow, d_qhigh, q, d_first_id, static_cast<hipStream_t>(stream));
 }
 
+int bivx_nearest_dev(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
+                     size_t q, uint32_t max_dist, uint32_t svtype, uint32_t *d_id, uint32_t *d_dist, void *stream) {
+  BIVX_TRY(check_query_args(idx, d_qlow, d_qhigh, q, "bivx_nearest_dev"));
+  if (q && !d_id) {
+    set_error("bivx_nearest_dev: null output");
+    return BIVX_E_INVALID;
+  }
+  if (svtype > 255u) {
+    set_error("bivx_nearest_dev: svtype %u out of range (0 = any, 1..255)", svtype);
+    return BIVX_E_INVALID;
+  }
+  BIVX_GUARD(idx);
+  note_reader(idx, static_cast<hipStream_t>(stream));
+  return launch_nearest(view_of(idx, svtype), d_qchrom, d_qlow, d_qhigh, q, max_dist, d_id, d_dist,
+                        static_cast<hipStream_t>(stream));
+}
+
 // ---- host-pointer convenience entry points -----------------------------------------------------------------
 
 namespace {
@@ -2023,6 +2040,52 @@ int bivx_any(const bivx_index *idx, const uint32_t *qchrom, const uint32_t *qlow
   BIVX_TRY(tmp.alloc(&d_first, q));
   BIVX_TRY(bivx_any_dev(idx, d.c, d.lo, d.hi, q, d_first, s));
   BIVX_HIP(hipMemcpyAsync(first_id_out, d_first, q * 4, hipMemcpyDeviceToHost, s));
+  BIVX_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int bivx_nearest(const bivx_index *idx, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh, size_t q,
+                 uint32_t max_dist, uint32_t svtype, uint32_t *id_out, uint32_t *dist_out) {
+  if (idx && idx->sharded) {
+    if (q && (!qlow || !qhigh || !id_out)) {
+      set_error("bivx_nearest: null argument");
+      return BIVX_E_INVALID;
+    }
+    return sharded_nearest(idx->sharded, qchrom, qlow, qhigh, q, max_dist, svtype, id_out, dist_out);
+  }
+  BIVX_TRY(check_query_args(idx, qlow, qhigh, q, "bivx_nearest"));
+  if (q == 0) return 0;
+  if (!id_out) {
+    set_error("bivx_nearest: null output");
+    return BIVX_E_INVALID;
+  }
+  BIVX_GUARD(idx);
+  LaneLease lease(idx);
+  hipStream_t s = lease.lane.stream;
+  if (q <= kMailboxQueries) {  // a handful of queries (the facade's find_nearest): through a mailbox, no copies
+    Mailbox mb(idx);
+    if (mb.host) {
+      uint32_t *h = static_cast<uint32_t *>(mb.host), *d = static_cast<uint32_t *>(mb.dev);
+      std::memcpy(h, qlow, q * 4);
+      std::memcpy(h + kMailboxQueries, qhigh, q * 4);
+      if (qchrom) std::memcpy(h + 2 * kMailboxQueries, qchrom, q * 4);
+      BIVX_TRY(bivx_nearest_dev(idx, qchrom ? d + 2 * kMailboxQueries : nullptr, d, d + kMailboxQueries, q, max_dist,
+                                svtype, d + 3 * kMailboxQueries, dist_out ? d + 4 * kMailboxQueries : nullptr, s));
+      BIVX_HIP(hipStreamSynchronize(s));
+      std::memcpy(id_out, h + 3 * kMailboxQueries, q * 4);
+      if (dist_out) std::memcpy(dist_out, h + 4 * kMailboxQueries, q * 4);
+      return 0;
+    }
+  }
+  TempPool tmp(idx, s);
+  DevQueries d;
+  BIVX_TRY(upload_queries(tmp, qchrom, qlow, qhigh, q, s, d));
+  uint32_t *d_id = nullptr, *d_dist = nullptr;
+  BIVX_TRY(tmp.alloc(&d_id, q));
+  if (dist_out) BIVX_TRY(tmp.alloc(&d_dist, q));
+  BIVX_TRY(bivx_nearest_dev(idx, d.c, d.lo, d.hi, q, max_dist, svtype, d_id, d_dist, s));
+  BIVX_HIP(hipMemcpyAsync(id_out, d_id, q * 4, hipMemcpyDeviceToHost, s));
+  if (dist_out) BIVX_HIP(hipMemcpyAsync(dist_out, d_dist, q * 4, hipMemcpyDeviceToHost, s));
   BIVX_HIP(hipStreamSynchronize(s));
   return 0;
 }

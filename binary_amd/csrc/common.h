@@ -133,6 +133,8 @@ int sharded_fill(const ShardedState *st, const uint32_t *qchrom, const uint32_t 
                  int sort_by_id);
 int sharded_any(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                 size_t q, uint32_t *first_id_out);
+int sharded_nearest(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
+                    size_t q, uint32_t max_dist, uint32_t svtype, uint32_t *id_out, uint32_t *dist_out);
 void sharded_stats(const ShardedState *st, bivx_stats *out);
 // the gathered device-resident CSR (bivx_query_sharded_dev)
 int sharded_query_dev(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
@@ -231,6 +233,9 @@ int launch_fill(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_
                 size_t q, const uint64_t *d_offsets, uint32_t *d_hits, hipStream_t s);
 int launch_any(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                size_t q, uint32_t *d_first, hipStream_t s);
+// nearest.hip: per query the interval of smallest (distance, id) within max_dist (bivx_nearest_dev); d_dist may be nullptr
+int launch_nearest(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
+                   size_t q, uint32_t max_dist, uint32_t *d_id, uint32_t *d_dist, hipStream_t s);
 // d_cond != nullptr: the pass runs only if *d_cond == seq (the single-pass kernel asks for it that way).
 // total_hint: the number of ids if the caller knows it (0: `cap` is taken as an upper bound; the kernel's LDS stage, and
 // with it how many wavefronts a CU holds, is sized by the average list)

@@ -474,6 +474,40 @@ static int any_impl(const ShardedState *st, const uint32_t *qchrom, const uint32
   });
 }
 
+// routed like any_impl; a chromosome lives on one shard whole, so its nearest interval is that shard's, and shard-local
+// append order is monotone in the global one, so the smallest id among equally near intervals maps to the smallest
+static int nearest_impl(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
+                        size_t q, uint32_t max_dist, uint32_t svtype, uint32_t *id_out, uint32_t *dist_out) {
+  if (!sharded_is_built(st)) {
+    set_error("bivx_nearest: index not built (call bivx_build after the last append)");
+    return BIVX_E_STATE;
+  }
+  if (svtype > 255u) {
+    set_error("bivx_nearest: svtype %u out of range (0 = any, 1..255)", svtype);
+    return BIVX_E_INVALID;
+  }
+  Route r;
+  BIVX_TRY(route(st, qchrom, q, r));
+  std::fill(id_out, id_out + q, BIVX_NO_HIT);
+  if (dist_out) std::fill(dist_out, dist_out + q, 0xFFFFFFFFu);
+  return on_every_shard(st, [&](size_t s) -> int {
+    if (r.qs[s].empty()) return 0;
+    SubBatch b;
+    std::vector<uint32_t> iaux;
+    gather(st, s, r.qs[s], qchrom, qlow, qhigh, nullptr, b, iaux);
+    const size_t m = r.qs[s].size();
+    std::vector<uint32_t> ids(m), dist(dist_out ? m : 0);
+    BIVX_TRY(bivx_nearest(st->shard[s], qchrom ? b.c.data() : nullptr, b.lo.data(), b.hi.data(), m, max_dist, svtype,
+                          ids.data(), dist_out ? dist.data() : nullptr));
+    for (size_t j = 0; j < m; ++j) {
+      if (ids[j] == BIVX_NO_HIT) continue;
+      id_out[r.qs[s][j]] = st->by_chrom ? st->gid[s][ids[j]] : ids[j];
+      if (dist_out) dist_out[r.qs[s][j]] = dist[j];
+    }
+    return 0;
+  });
+}
+
 
 // ---- bivx_query_sharded_dev: every shard answers on its device, RCCL gathers the CSRs into devices[0] --------------------
 
@@ -1084,6 +1118,11 @@ int sharded_fill(const ShardedState *st, const uint32_t *qchrom, const uint32_t 
 int sharded_any(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                 size_t q, uint32_t *first_id_out) {
   return no_throw("bivx_any", [&] { return any_impl(st, qchrom, qlow, qhigh, q, first_id_out); });
+}
+int sharded_nearest(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
+                    size_t q, uint32_t max_dist, uint32_t svtype, uint32_t *id_out, uint32_t *dist_out) {
+  return no_throw("bivx_nearest",
+                  [&] { return nearest_impl(st, qchrom, qlow, qhigh, q, max_dist, svtype, id_out, dist_out); });
 }
 int sharded_query_dev(const ShardedState *st, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh,
                       size_t q, int sort_by_id, bivx_sharded_result *out) {

@@ -234,6 +234,51 @@ class IntervalIndex:
         capi.check(self._L.bivx_any(self._h, _ptr(qc), _ptr(qlow), _ptr(qhigh), qlow.size, _ptr(first)))
         return first
 
+    @staticmethod
+    def _max_dist(max_dist) -> int:
+        if max_dist is None:
+            return 0xFFFFFFFF
+        if not 0 <= int(max_dist) <= 0xFFFFFFFF:
+            raise ValueError("max_dist must lie in 0 .. 2^32 - 1 (None: unbounded)")
+        return int(max_dist)
+
+    def nearest(self, qlow, qhigh, qchrom=None, max_dist=None, svtype: int = 0):
+        """Per query the nearest stored interval (bivx_nearest, include/bivx.h): (ids uint32[q], dists uint32[q]). The
+        distance is max(0, q.low - high, low - q.high); ties go to the smallest id; ids[i] == capi.BIVX_NO_HIT when no
+        interval of the query's chromosome (and of svtype, if not 0) lies within max_dist (None: unbounded)."""
+        self._ensure_built()
+        qlow, qhigh = _u32(qlow).ravel(), _u32(qhigh).ravel()
+        if qlow.shape != qhigh.shape:
+            raise ValueError("qlow and qhigh must have the same length")
+        qc = None if qchrom is None else _u32(qchrom).ravel()
+        if qc is not None and qc.shape != qlow.shape:
+            raise ValueError("qchrom must have the same length as qlow")
+        ids = np.empty(qlow.size, dtype=np.uint32)
+        dists = np.empty(qlow.size, dtype=np.uint32)
+        capi.check(self._L.bivx_nearest(self._h, _ptr(qc), _ptr(qlow), _ptr(qhigh), qlow.size, self._max_dist(max_dist),
+                                        int(svtype), _ptr(ids), _ptr(dists)))
+        return ids, dists
+
+    def nearest_device(self, qlow, qhigh, qchrom=None, max_dist=None, svtype: int = 0, ids=None, dists=None):
+        """nearest() on device tensors (bivx_nearest_dev): one launch on the current stream, asynchronous. Returns
+        (ids, dists) as int32 device tensors holding the uint32 values (allocated when not given)."""
+        self._ensure_built()
+        q = qlow.numel()
+        _check_dev_tensor(qlow, "qlow")
+        _check_dev_tensor(qhigh, "qhigh", q)
+        if qchrom is not None:
+            _check_dev_tensor(qchrom, "qchrom", q)
+        if ids is None:
+            ids = torch.empty(q, dtype=torch.int32, device=qlow.device)
+        if dists is None:
+            dists = torch.empty(q, dtype=torch.int32, device=qlow.device)
+        _check_dev_tensor(ids, "ids", q)
+        _check_dev_tensor(dists, "dists", q)
+        s = C.c_void_p(torch.cuda.current_stream(qlow.device).cuda_stream)
+        capi.check(self._L.bivx_nearest_dev(self._h, _tptr(qchrom), _tptr(qlow), _tptr(qhigh), q,
+                                            self._max_dist(max_dist), int(svtype), _tptr(ids), _tptr(dists), s))
+        return ids, dists
+
     # ---- query side, device tensors (no host round trip except the hit total) --------------------------
     def count_overlaps_device(self, qlow, qhigh, qchrom=None, offsets=None):
         """offsets int64[q+1] on the device (exclusive prefix of hit counts); asynchronous."""

@@ -18,7 +18,8 @@
 //     red-black tree (rb_tree.hpp) that is replayed from the insertion sequence the first time it is asked for.
 //   - keys must be std::uint32_t or std::int32_t and is_overlap must not be overridden: the device evaluates
 //     the default predicate. There is no CPU fallback for the query path; without a GPU construction throws.
-//   - new: find_overlaps_batch(...) answers many queries in one device pass (that is the fast path).
+//   - new: find_overlaps_batch(...) answers many queries in one device pass (that is the fast path); find_nearest(q
+//     [, max_distance]) returns the nearest stored interval (bivx_nearest).
 #ifndef BINARY_AMD_ALGORITHM_INTERVAL_TREE_HPP_
 #define BINARY_AMD_ALGORITHM_INTERVAL_TREE_HPP_
 
@@ -261,6 +262,19 @@ namespace binary::algorithm::tree {
       return find_overlap(interval_type{std::forward<Args>(args)...});
     }
 
+    /// New (no reference counterpart): the stored interval nearest to q — smallest distance max(0, q.low - high,
+    /// low - q.high), 0 when they overlap — and among equally near ones the one inserted first (bivx_nearest, one device
+    /// call). nullopt only when the tree is empty, or, with max_distance (in key units), when every interval is farther.
+    /// Keys other than 32-bit ones: a query end outside the tree's coordinate window is clamped to the window's edge,
+    /// which adds the same amount to every stored interval's distance and so keeps the answer; max_distance is then
+    /// compared with the true distance on the host. (Queries with low <= high, BaseInterval's invariant.)
+    [[nodiscard]] auto find_nearest(interval_type const &q) const -> std::optional<interval_type> {
+      return nearest(q, nullptr);
+    }
+    [[nodiscard]] auto find_nearest(interval_type const &q, key_type max_distance) const -> std::optional<interval_type> {
+      return nearest(q, &max_distance);
+    }
+
     /// Accepts lvalues and rvalues (the reference only compiles for rvalues, interval_tree.hpp:161).
     [[nodiscard]] auto find_overlaps(interval_type const &q) const -> std::vector<interval_type> {
       const OverlapBatch b = find_overlaps_batch(std::span<const interval_type>(&q, 1));
@@ -378,6 +392,41 @@ namespace binary::algorithm::tree {
         hi = q.high > top_ ? map_key(top_) : map_key(q.high);
         return true;
       }
+    }
+
+    auto nearest(interval_type const &q, const key_type *max_distance) const -> std::optional<interval_type> {
+      if constexpr (std::is_signed_v<key_type>)
+        if (max_distance != nullptr && *max_distance < key_type{0}) return std::nullopt;
+      sync();
+      std::uint32_t lo = 0, hi = 0, md = BIVX_NO_HIT;  // (UINT32_MAX: unbounded)
+      if constexpr (kNative32) {
+        // the uint32 / int32 map keeps differences: device distances are key distances
+        lo = detail::to_u32(q.low);
+        hi = detail::to_u32(q.high);
+        if (max_distance != nullptr) md = static_cast<std::uint32_t>(*max_distance);
+      } else {
+        if (!have_window_) return std::nullopt;
+        // NOT map_query: a query beyond every coordinate still has a nearest interval
+        const std::uint64_t b = widen(base_), t = widen(top_);
+        auto clamp = [&](key_type k) {
+          const std::uint64_t w = widen(k);
+          return static_cast<std::uint32_t>((w < b ? b : w > t ? t : w) - b);
+        };
+        lo = clamp(q.low);
+        hi = clamp(q.high);
+      }
+      std::uint32_t id = BIVX_NO_HIT;
+      detail::check(bivx_nearest(index_.get(), nullptr, &lo, &hi, 1, md, 0, &id, nullptr), "bivx_nearest");
+      if (id == BIVX_NO_HIT) return std::nullopt;
+      if constexpr (!kNative32) {
+        if (max_distance != nullptr) {  // the true distance, in key units (widen keeps differences)
+          const interval_type &i = items_[id];
+          const std::uint64_t ql = widen(q.low), qh = widen(q.high), il = widen(i.low), ih = widen(i.high);
+          const std::uint64_t d = std::max(ql > ih ? ql - ih : 0ull, il > qh ? il - qh : 0ull);
+          if (d > static_cast<std::uint64_t>(*max_distance)) return std::nullopt;
+        }
+      }
+      return items_[id];
     }
 
     void push(interval_type &&i) {

@@ -56,8 +56,9 @@ typedef enum bivx_status {
 #define BIVX_MAX_CHROMS 65536u
 #define BIVX_NO_HIT 0xFFFFFFFFu
 
-/* ABI version of this header: major << 16 | minor. (2.3 also carries bivx_query_sharded_dev_q; the minor goes up with the
- * next change that moves the version's pin.) */
+/* ABI version of this header: major << 16 | minor. (2.3 also carries bivx_query_sharded_dev_q, bivx_nearest and
+ * bivx_nearest_dev: additions only, source- and binary-compatible; the minor goes up with the next change that moves the
+ * version's pin.) */
 #define BIVX_ABI_VERSION 0x00020003u
 uint32_t bivx_abi_version(void);
 const char *bivx_last_error(void);
@@ -81,7 +82,7 @@ void bivx_release_pooled(void);
  * LPT on their interval counts; a query is answered by the device that holds its chromosome; no data
  * moves between devices. An index with fewer populated chromosomes than devices (a plain IntervalTree has one) is
  * replicated on every device and the queries are split instead. The handle takes the HOST-pointer entry points
- * (bivx_append*, bivx_build, bivx_count*, bivx_fill*, bivx_find_overlaps, bivx_any, bivx_get_*, bivx_get_stats), with
+ * (bivx_append*, bivx_build, bivx_count*, bivx_fill*, bivx_find_overlaps, bivx_any, bivx_nearest, bivx_get_*, bivx_get_stats), with
  * the same ids and results as a single-device index; the `_dev` entry points address one device's memory and return
  * BIVX_E_STATE for it. One host thread per device drives its shard. devices may name a device more than once.
  * (Across PROCESSES — one rank per GPU — shard with the same LPT and gather with RCCL: binary_amd/sharding.py.) */
@@ -259,6 +260,29 @@ int bivx_any(const bivx_index *idx, const uint32_t *qchrom, const uint32_t *qlow
              size_t q, uint32_t *first_id_out);
 int bivx_any_dev(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t *d_qlow,
                  const uint32_t *d_qhigh, size_t q, uint32_t *d_first_id, void *stream);
+
+/* ---- query side: nearest interval ----------------------------------------------------------------
+ * replaces: what a caller of find_overlaps emulates today by widening a query until it meets something (bedtools
+ * closest, GenomicRanges / pyranges nearest; sv2nl's distances, standalone/sv2nl --dis). The distance of query
+ * q = [q.low, q.high] and stored interval i = [low, high] on the same chromosome is
+ *     d(q, i) = max(0, q.low - high, low - q.high)      (exact integer arithmetic, never wraps; fits uint32_t)
+ * d == 0 exactly when the overlap predicate q.low <= high && low <= q.high holds (intervals and queries with low > high
+ * included). The nearest interval of q is, among the intervals on q's chromosome (and of the selected svtype) with
+ * d <= max_dist, the one of smallest (d, id): ties go to the smallest append-order id, so the answer does not depend on
+ * the build order, the kernel or the device count. max_dist == UINT32_MAX: unbounded. id_out[i] = BIVX_NO_HIT when no
+ * interval qualifies (empty chromosome, a type the index does not hold, everything too far); dist_out[i] is then
+ * 0xFFFFFFFF — test the id, not the distance, which may be that value for a real answer. With max_dist == 0 the ids
+ * are bivx_any's bit for bit (smallest overlapping id).
+ * svtype: 0 = intervals of every type, t in 1..255 = only those appended with svtype t (as bivx_filter::svtype).
+ * qchrom may be NULL (every query on chromosome 0); dist_out / d_dist may be NULL. BIVX_E_STATE before build;
+ * BIVX_E_INVALID for null columns or outputs with q > 0, or svtype > 255. bivx_nearest takes a sharded handle (routed
+ * like bivx_any: by chromosome, or the batch split over a replicated index; global ids); bivx_nearest_dev is one
+ * launch on `stream`, allocates nothing, takes no workspace, never synchronises, and returns BIVX_E_STATE for a
+ * sharded handle. Algorithm and measurements: DESIGN.md, "Nearest interval". */
+int bivx_nearest(const bivx_index *idx, const uint32_t *qchrom, const uint32_t *qlow, const uint32_t *qhigh, size_t q,
+                 uint32_t max_dist, uint32_t svtype, uint32_t *id_out, uint32_t *dist_out);
+int bivx_nearest_dev(const bivx_index *idx, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
+                     size_t q, uint32_t max_dist, uint32_t svtype, uint32_t *d_id, uint32_t *d_dist, void *stream);
 
 /* ---- fused post-filters ---------------------------------------------------------------------------
  * replaces: the check_condition step that sv2nl applies to every find_overlaps hit
