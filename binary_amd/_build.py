@@ -8,7 +8,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_PKG, "csrc")
 # BIVX_LIB: a variant build to load instead (tools/build_variant.sh; A/B measurements only)
 LIB_PATH = os.environ.get("BIVX_LIB") or os.path.join(_PKG, "libbivx.so")
-_SOURCES = ("scan.hip", "build.hip", "query.hip", "query_fused.hip", "query_pipe.hip", "route.hip", "nearest.hip", "prefix_device.h", "query_device.h", "wave_device.h", "capi.hip", "sharded.cpp", "common.h",
+_SOURCES = ("scan.hip", "build.hip", "query.hip", "query_fused.hip", "query_pipe.hip", "route.hip", "nearest.hip", "prefix_device.h", "query_device.h", "query_route.h", "wave_device.h", "capi.hip", "sharded.cpp", "common.h",
             "Makefile")
 
 

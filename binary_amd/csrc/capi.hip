@@ -1442,8 +1442,10 @@ int query_single_pass(const bivx_index *idx, const uint32_t *d_qchrom, const uin
     d_workspace = it->second.p;
     self_clean = true;
   }
-  return launch_query_fused(view, d_qchrom, d_qlow, d_qhigh, q, d_offsets, d_hit_ids, hit_capacity, d_workspace,
-                            self_clean, sort_by_id != 0, s, d_counts, d_total);
+  const RouteKnobs knobs = read_route_knobs();
+  const Plan plan = plan_single_pass(shape_of(view), q, hit_capacity, sort_by_id != 0, d_counts != nullptr, knobs);
+  return launch_single_pass(plan, knobs, view, d_qchrom, d_qlow, d_qhigh, q, d_offsets, d_hit_ids, hit_capacity,
+                            d_workspace, self_clean, sort_by_id != 0, s, d_counts, d_total);
 }
 }  // namespace
 
@@ -1480,7 +1482,8 @@ int bivx_self_overlaps_dev(const bivx_index *idx, int sort_by_id, uint64_t *d_of
   }
   const size_t n = idx->built_n;
   const IndexView view = view_of(idx);
-  if (n == 0 || !self_overlaps_eligible(view, n))  // the general path: the appended columns are the batch
+  const RouteKnobs knobs = read_route_knobs();
+  if (n == 0 || !plan_self_overlaps(shape_of(view), n, knobs))  // the general path: the appended columns are the batch
     return query_single_pass(idx, idx->d_chrom, idx->d_low, idx->d_high, n, nullptr, sort_by_id, d_offsets, nullptr,
                              d_hit_ids, hit_capacity, nullptr, nullptr, 0, stream, "bivx_self_overlaps_dev");
   BIVX_GUARD(idx);
@@ -1551,7 +1554,7 @@ int bivx_self_overlaps_dev(const bivx_index *idx, int sort_by_id, uint64_t *d_of
   // one pass in slot order (lists back to back in d_tmp; per id ONE word: the list's length above where it begins), offsets =
   // a scan of the lengths, then the lists are gathered into id order
   BIVX_TRY(launch_self_overlaps(view, q, q + n, q + 2 * n, idx->d_id, n, d_src, d_offsets, hit_capacity ? d_tmp : nullptr,
-                                hit_capacity, static_cast<uint64_t *>(ws), true, s));
+                                hit_capacity, static_cast<uint64_t *>(ws), true, knobs, s));
   if (!hit_capacity) {
     BIVX_TRY(exclusive_scan_lengths_u64(d_src, d_offsets, n, scan_scr, s));
   } else {
@@ -1628,11 +1631,7 @@ const char *bivx_query_kernel_name(const bivx_index *idx, size_t q, uint64_t hit
   if (!idx || idx->sharded || !idx->built) return "";
   IndexView view;
   if (view_with_filter(idx, filter, view) != 0) return "";
-  if (pipe_eligible(view, q, hit_capacity, sort_by_id != 0, false)) return "k_query_pipe";
-  const bool ms = pipe_ms_eligible(view, q, hit_capacity, false);
-  if (pipe_dense_eligible(view, q, hit_capacity, sort_by_id != 0, false))
-    return ms ? "k_query_pipe_dense|k_query_pipe_ms" : "k_query_pipe_dense|k_query_fused";
-  return ms ? "k_query_pipe_ms" : "k_query_fused";
+  return route_name(plan_single_pass(shape_of(view), q, hit_capacity, sort_by_id != 0, false, read_route_knobs()).route);
 }
 
 int bivx_sort_hits_dev(const bivx_index *idx, const uint64_t *d_offsets, uint32_t *d_hit_ids, size_t q, void *stream) {

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/bivx.h"
+#include "query_route.h"
 
 namespace bivx {
 
@@ -241,40 +242,37 @@ int launch_nearest(const IndexView &v, const uint32_t *d_qchrom, const uint32_t 
 // with it how many wavefronts a CU holds, is sized by the average list)
 int launch_sort_hits(const uint64_t *d_offsets, uint32_t *d_hits, size_t q, uint64_t cap, hipStream_t s,
                      const uint32_t *d_cond = nullptr, uint32_t seq = 0, uint64_t total_hint = 0);
-// single pass: offsets[q+1] and hits (slots below cap only) in one kernel; ws: fused_workspace_bytes(q)
+// single pass: offsets[q+1] and hits (slots below cap only); ws: fused_workspace_bytes(q). Carries out a plan
+// (query_route.h) in launches of plan.per_launch queries.
 size_t fused_workspace_bytes(size_t q);
-int launch_query_fused(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow,
-                       const uint32_t *d_qhigh, size_t q, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap,
-                       void *d_ws, bool self_clean, bool sort_ids, hipStream_t s, uint32_t *d_counts = nullptr,
-                       uint64_t *d_total = nullptr);  // d_counts != nullptr: unordered begin/count output
+RouteShape shape_of(const IndexView &v);
+int launch_single_pass(const Plan &plan, const RouteKnobs &knobs, const IndexView &v, const uint32_t *d_qchrom,
+                       const uint32_t *d_qlow, const uint32_t *d_qhigh, size_t q, uint64_t *d_offsets, uint32_t *d_hits,
+                       uint64_t cap, void *d_ws, bool self_clean, bool sort_ids, hipStream_t s,
+                       uint32_t *d_counts = nullptr, uint64_t *d_total = nullptr);  // d_counts != nullptr: unordered begin/count output
 
-// query_pipe.hip: the pipelined single-pass kernel for the common case; launch_query_fused dispatches to it
-bool pipe_eligible(const IndexView &v, size_t q, uint64_t cap, bool sort_ids, bool unordered);
-size_t pipe_queries_per_launch();
-size_t pipe_ms_queries_per_launch();  // (k_query_pipe_ms has tiles of its own size)
-bool pipe_dense_eligible(const IndexView &v, size_t q, uint64_t cap, bool sort_ids, bool unordered);
+// query_pipe.hip: the pipelined single-pass kernels launch_single_pass dispatches to (knobs: BIVX_PIPE_WGS)
 int launch_query_pipe_dense(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                             size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                            int flags, uint32_t seq, hipStream_t s);
+                            int flags, uint32_t seq, const RouteKnobs &knobs, hipStream_t s);
 // ... and for everything else that is large: several segments per chromosome, fused filters, many ids per query
 // (skip_seq != 0: launched behind k_query_pipe_dense, returns if that kernel took the launch)
-bool pipe_ms_eligible(const IndexView &v, size_t q, uint64_t cap, bool unordered);
 int launch_query_pipe_ms(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                          size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                         int flags, uint32_t skip_seq, hipStream_t s);
+                         int flags, uint32_t skip_seq, const RouteKnobs &knobs, hipStream_t s);
 // The index overlapped with itself (queries = its intervals in slot order, results wanted in id order: d_perm = the slots'
 // ids): k_query_pipe_dense writes the lists in slot order into d_tmp_hits and leaves d_src_by_id[id] = a list's length <<
 // kSelfPosBits | where it begins (cap == 0: the lengths only); launch_permute_lists then gathers list i to d_hits[offsets[i]].
-bool self_overlaps_eligible(const IndexView &v, size_t n);
 int launch_self_overlaps(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                          const uint32_t *d_perm, size_t n, uint64_t *d_src_by_id,
                          uint64_t *d_offsets_scratch, uint32_t *d_tmp_hits, uint64_t cap, uint64_t *ws, bool self_clean,
-                         hipStream_t s);
+                         const RouteKnobs &knobs, hipStream_t s);
 // also leaves d_offsets (n + 1): the exclusive prefix sum of the lists' lengths (d_scan: scan_scratch_bytes(n))
 int launch_permute_lists(uint64_t *d_offsets, const uint64_t *d_src, const uint32_t *d_tmp, uint32_t *d_hits, size_t n,
                          uint64_t cap, bool sort_ids, bool *sorted, void *d_scan, hipStream_t s);
 int launch_query_pipe(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                       size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                      int flags, uint32_t sort_seq, uint32_t *d_counts, uint64_t *d_total, hipStream_t s);
+                      int flags, uint32_t sort_seq, uint32_t *d_counts, uint64_t *d_total, const RouteKnobs &knobs,
+                      hipStream_t s);
 
 }  // namespace bivx

@@ -8,7 +8,6 @@
 namespace bivx {
 namespace {
 
-constexpr unsigned kFMaxTiles = 65536;                 // tiles of 1024 queries per launch (ordered output)
 constexpr unsigned kFMaxGroups = kFMaxTiles / kWave;   // groups of 64 tiles
 constexpr unsigned kFlatTiles = 1024;                  // launches up to this many tiles sweep the tile words directly
 constexpr uint64_t kStValid = 1ull << 63;

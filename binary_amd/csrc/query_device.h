@@ -630,7 +630,6 @@ constexpr uint32_t kRankBlock = 8;   // elements ranked per sweep of a list (hel
 #ifndef BIVX_FUSED_RANK_BLOCK
 #define BIVX_FUSED_RANK_BLOCK 8
 #endif
-constexpr uint32_t kFusedSortMaxAvg = 6;   // ids per query (by buffer capacity) up to which k_query_fused orders ids itself
 constexpr uint32_t kFusedRankBlock = BIVX_FUSED_RANK_BLOCK;  // the same inside k_query_fused, which lives in 64 VGPRs
 constexpr uint32_t kSortLane = 24;    // <= this many hits: the owning lane insertion-sorts in place
 constexpr uint32_t kSortLds = 4096;   // <= this many: the wavefront bitonic-sorts through LDS (16 KiB per wavefront)

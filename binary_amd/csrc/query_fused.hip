@@ -4,7 +4,6 @@
 // bivx_count_dev (zero-capacity buffer). Replaces a batch of IntervalTree::find_overlaps calls (reference
 // interval_tree.hpp:306-334). Device building blocks: query_device.h.
 #include <atomic>
-#include <cstdlib>
 
 #include "query_device.h"
 #include "prefix_device.h"
@@ -27,10 +26,7 @@ namespace {
 //   hits of group g; ws[kWsStatus + kFMaxGroups + t]: kStValid | hits of tile t. Each is written and polled as ONE
 //   8-byte agent-scope atomic, so the value needs no separate fence. Tiles take tickets in launch order: every
 //   predecessor of a polling tile is already resident, the wait cannot deadlock; spins are bounded anyway.
-#ifndef BIVX_FUSED_THREADS
-#define BIVX_FUSED_THREADS 1024
-#endif
-constexpr int kFThreads = BIVX_FUSED_THREADS;
+constexpr int kFThreads = BIVX_FUSED_THREADS;  // (query_route.h)
 #ifndef BIVX_FUSED_WAVES
 #define BIVX_FUSED_WAVES 8  // waves per SIMD the register allocation is held to: 8 = two workgroups per CU, 64 VGPRs
 #endif
@@ -38,6 +34,7 @@ constexpr int kFWaves = kFThreads / kWave;
 // One query per thread. (More per thread was measured and did not pay: a wavefront here is latency-bound, and the
 // output staging below relies on the 64 lists of a wavefront being adjacent.)
 constexpr int kFTile = kFThreads;
+static_assert(kFTile == kFusedTile, "query_route.h plans launches of kFusedTile queries per tile");
 constexpr uint32_t kStage = 512;     // ids a wavefront lays out in LDS per round before streaming them out
 #ifndef BIVX_GATHER
 #define BIVX_GATHER 8
@@ -440,9 +437,15 @@ size_t fused_workspace_bytes(size_t q) {
   return ((size_t)kWsList + kWsListWords) * sizeof(uint64_t);
 }
 
-int launch_query_fused(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow,
-                       const uint32_t *d_qhigh, size_t q, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap,
-                       void *d_ws, bool self_clean, bool sort_ids, hipStream_t s, uint32_t *d_counts,
+RouteShape shape_of(const IndexView &v) {
+  const ptrdiff_t delta = reinterpret_cast<const char *>(v.rec) - reinterpret_cast<const char *>(v.se);
+  return RouteShape{v.flt_kind != BIVX_FILTER_NONE, v.max_segs, fits_lds(v), v.nslots, v.max_cell, v.max_window,
+                    delta >= 0 && (uint64_t)delta + ((uint64_t)v.nslots + 2) * 8 <= 0xFFFFFFFFull};
+}
+
+int launch_single_pass(const Plan &plan, const RouteKnobs &knobs, const IndexView &v, const uint32_t *d_qchrom,
+                       const uint32_t *d_qlow, const uint32_t *d_qhigh, size_t q, uint64_t *d_offsets, uint32_t *d_hits,
+                       uint64_t cap, void *d_ws, bool self_clean, bool sort_ids, hipStream_t s, uint32_t *d_counts,
                        uint64_t *d_total) {
   const bool unordered = d_counts != nullptr;  // begin/count output, see k_query_fused
   if (q == 0) {
@@ -450,69 +453,38 @@ int launch_query_fused(const IndexView &v, const uint32_t *d_qchrom, const uint3
     return 0;
   }
   uint64_t *ws = static_cast<uint64_t *>(d_ws);
-  // ordered output: a launch is limited to the tiles one prefix sweep covers; unordered output has no such limit
-  // (only the departure count's 20 bits in ws[kWsDone])
-  unsigned max_tiles = unordered ? (1u << 19) : kFMaxTiles, max_tiles_pipe = kFMaxTiles;
-  if (const char *e = std::getenv("BIVX_MAX_TILES_PER_LAUNCH")) {  // test knob: forces the chained-launch path
-    const long v = std::atol(e);
-    if (v >= 1 && v < (long)max_tiles) max_tiles = (unsigned)v;
-    if (v >= 1 && v < (long)max_tiles_pipe) max_tiles_pipe = (unsigned)v;
-  }
-  // the common case (one segment per chromosome, no filter, few ids per query) has a pipelined kernel with tiles of its
-  // own size (begin / count output through it is one launch: there is no entry q_end to chain launches through)
-  const size_t pipe_tile = pipe_queries_per_launch() / kFMaxTiles;
-  const bool use_pipe = pipe_eligible(v, q, cap, sort_ids, unordered) && !(unordered && q > pipe_tile * max_tiles_pipe);
-  // ... and so has the case of many ids per query if the batch is position-sorted, which a device-side probe finds out:
-  // both kernels are launched, one of them returns at once
-  const bool try_dense = !use_pipe && pipe_dense_eligible(v, q, cap, sort_ids, unordered);
-  // ... and so has everything else that is large (several segments per chromosome, fused filters, many ids per query in
-  // any order): a position-sorted batch is left to the dense kernel (which leaves the word for this one to see)
-  const bool use_ms = !use_pipe && pipe_ms_eligible(v, q, cap, unordered);
-  const size_t ms_tile = pipe_ms_queries_per_launch() / kFMaxTiles;
-  // (a launch pair k_query_pipe_dense | k_query_pipe_ms is cut at the smaller of the two kernels' limits)
-  const size_t per_launch = use_ms ? ms_tile * max_tiles_pipe
-                                   : use_pipe || try_dense ? pipe_tile * max_tiles_pipe : (size_t)max_tiles * kFTile;
+  const bool use_pipe = plan.route == QueryRoute::Pipe;
+  // (a dense route launches both kernels, one of them returns at once; a position-sorted batch is left to the dense
+  // kernel, which leaves the word for the second one to see)
+  const bool try_dense = plan.route == QueryRoute::DenseFused || plan.route == QueryRoute::DenseMs;
+  const bool use_ms = plan.route == QueryRoute::Ms || plan.route == QueryRoute::DenseMs;
   // caller's workspace: zeroed in front of every launch (ordered output), or once per call (unordered output:
   // the running total lives in it across the call's launches)
   if (!self_clean && unordered && !use_pipe) BIVX_HIP(hipMemsetAsync(d_ws, 0, (size_t)kWsStatus * sizeof(uint64_t), s));
-  for (size_t q0 = 0; q0 < q; q0 += per_launch) {
-    const size_t q1 = q0 + per_launch < q ? q0 + per_launch : q;
-    const size_t tile_q = use_pipe ? pipe_queries_per_launch() / kFMaxTiles : (size_t)kFTile;
-    const unsigned tiles = (unsigned)((q1 - q0 + tile_q - 1) / tile_q);
-    const size_t tile_small = use_ms ? ms_tile : use_pipe || try_dense ? pipe_queries_per_launch() / kFMaxTiles : (size_t)kFTile;
+  for (size_t q0 = 0; q0 < q; q0 += plan.per_launch) {
+    const size_t q1 = q0 + plan.per_launch < q ? q0 + plan.per_launch : q;
     if (!self_clean && (!unordered || use_pipe))
-      BIVX_HIP(hipMemsetAsync(d_ws, 0, ((q1 - q0 + tile_small - 1) / tile_small + kFMaxGroups + kWsStatus) * sizeof(uint64_t), s));
-    const dim3 grid(tiles), block(kFThreads);
-    const bool lds = fits_lds(v), flt = v.flt_kind != BIVX_FILTER_NONE;
-    // BIVX_PREFIX_WAIT_LOG2 (tests): bound of a prefix wait as log2 of 10 ns ticks; 1 makes every wait that is not
-    // satisfied at once expire, which is how the error path is exercised
-    int wait_log2 = 0;
-    if (const char *e = std::getenv("BIVX_PREFIX_WAIT_LOG2")) {
-      const long w = std::atol(e);
-      if (w > 0 && w < 64) wait_log2 = (int)w;
-    }
-    const int flags = (self_clean ? kFlagSelfClean : 0) | (q1 == q ? kFlagFinal : 0) | (wait_log2 << kFlagWaitShift);
-    // Ordering ids inside the kernel pays while a wavefront's 64 lists fit half its output stage (one round, all
-    // lanes busy); the buffer capacity is the only bound on the hit count the host has. Denser results are
-    // ordered by k_sort_hits afterwards, whose stage is eight times larger.
-    const bool sort_inside = sort_ids && !unordered && !use_ms && cap <= (uint64_t)kFusedSortMaxAvg * q;
+      BIVX_HIP(hipMemsetAsync(d_ws, 0, ((q1 - q0 + plan.tile_q - 1) / plan.tile_q + kFMaxGroups + kWsStatus) * sizeof(uint64_t), s));
+    const int flags = (self_clean ? kFlagSelfClean : 0) | (q1 == q ? kFlagFinal : 0) | (knobs.wait_log2 << kFlagWaitShift);
     static std::atomic<uint32_t> launch_seq{1};
     uint32_t seq = launch_seq.fetch_add(1);
     if (seq == 0) seq = launch_seq.fetch_add(1);  // 0 is what a cleared workspace holds
     uint32_t skip_seq = 0;
     if (try_dense) {
-      if (int rc = launch_query_pipe_dense(v, d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, flags, seq, s))
+      if (int rc = launch_query_pipe_dense(v, d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, flags, seq, knobs, s))
         return rc;
       skip_seq = seq;
     }
     if (use_pipe) {
       if (int rc = launch_query_pipe(v, d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, flags,
-                                     sort_ids ? seq : 0u, d_counts, d_total, s))
+                                     sort_ids ? seq : 0u, d_counts, d_total, knobs, s))
         return rc;
     } else if (use_ms) {
-      if (int rc = launch_query_pipe_ms(v, d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, flags, skip_seq, s))
+      if (int rc = launch_query_pipe_ms(v, d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, flags, skip_seq, knobs, s))
         return rc;
     } else {
+      const dim3 grid((unsigned)((q1 - q0 + kFTile - 1) / kFTile)), block(kFThreads);
+      const bool lds = fits_lds(v), flt = v.flt_kind != BIVX_FILTER_NONE;
 #define BIVX_LAUNCH_FUSED_V(L, FL, SO, MSV, UV)                                                               \
   hipLaunchKernelGGL((k_query_fused<L, FL, SO, MSV, UV>), grid, block, 0, s, v, d_qchrom, d_qlow, d_qhigh, q0, \
                      q1, d_offsets, d_hits, cap, ws, flags, d_counts, d_total, seq, skip_seq)
@@ -527,20 +499,16 @@ int launch_query_fused(const IndexView &v, const uint32_t *d_qchrom, const uint3
   } else {                                                 \
     BIVX_LAUNCH_FUSED_V(L, FL, SO, false, false);          \
   }
-#ifdef BIVX_ONLY_MAIN  // development builds (tools/resource_usage.py): only the headline instantiation
-    BIVX_LAUNCH_FUSED_V(true, false, false, false, false);
-#else
-    switch ((lds ? 4 : 0) | (flt ? 2 : 0) | (sort_inside ? 1 : 0)) {
-      case 0: BIVX_LAUNCH_FUSED(false, false, false); break;
-      case 1: BIVX_LAUNCH_FUSED(false, false, true); break;
-      case 2: BIVX_LAUNCH_FUSED(false, true, false); break;
-      case 3: BIVX_LAUNCH_FUSED(false, true, true); break;
-      case 4: BIVX_LAUNCH_FUSED(true, false, false); break;
-      case 5: BIVX_LAUNCH_FUSED(true, false, true); break;
-      case 6: BIVX_LAUNCH_FUSED(true, true, false); break;
-      default: BIVX_LAUNCH_FUSED(true, true, true); break;
-    }
-#endif
+      switch ((lds ? 4 : 0) | (flt ? 2 : 0) | (plan.sort_inside ? 1 : 0)) {
+        case 0: BIVX_LAUNCH_FUSED(false, false, false); break;
+        case 1: BIVX_LAUNCH_FUSED(false, false, true); break;
+        case 2: BIVX_LAUNCH_FUSED(false, true, false); break;
+        case 3: BIVX_LAUNCH_FUSED(false, true, true); break;
+        case 4: BIVX_LAUNCH_FUSED(true, false, false); break;
+        case 5: BIVX_LAUNCH_FUSED(true, false, true); break;
+        case 6: BIVX_LAUNCH_FUSED(true, true, false); break;
+        default: BIVX_LAUNCH_FUSED(true, true, true); break;
+      }
 #undef BIVX_LAUNCH_FUSED
 #undef BIVX_LAUNCH_FUSED_V
     }
@@ -548,7 +516,7 @@ int launch_query_fused(const IndexView &v, const uint32_t *d_qchrom, const uint3
       BIVX_HIP(hipGetLastError());
       // ordered inside the kernel: the pass only runs if a wavefront asked for it (it compares the word with seq)
       if (int rc = launch_sort_hits(d_offsets + q0, d_hits, q1 - q0, cap, s,
-                                    sort_inside ? reinterpret_cast<const uint32_t *>(ws + kWsNeedSort) : nullptr, seq))
+                                    plan.sort_inside ? reinterpret_cast<const uint32_t *>(ws + kWsNeedSort) : nullptr, seq))
         return rc;
     }
   }

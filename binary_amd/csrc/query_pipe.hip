@@ -27,7 +27,6 @@
 // workgroups; the smallest unpublished tile can therefore always be finished. Waits on other workgroups are bounded
 // by wall time and an expired one fails the call (prefix_device.h).
 #include <atomic>
-#include <cstdlib>
 
 #include "prefix_device.h"
 #include "query_device.h"
@@ -35,40 +34,24 @@
 namespace bivx {
 namespace {
 
-#ifndef BIVX_PIPE_THREADS
-#define BIVX_PIPE_THREADS 1024  // (experiments: 512 = seven workers and the service wavefront)
-#endif
-constexpr int kPThreads = BIVX_PIPE_THREADS;
+constexpr int kPThreads = BIVX_PIPE_THREADS;  // (query_route.h)
 constexpr int kPWaves = kPThreads / kWave;
 constexpr int kWorkers = kPWaves - 1;          // wavefront kWorkers is the service wavefront
 constexpr uint32_t kPTile = kWorkers * kWave;  // 960 queries
+static_assert(kPTile == kPipeTile, "query_route.h plans launches of kPipeTile queries per tile");
 constexpr uint32_t kRing = 8;                  // tile slots in LDS
-#ifndef BIVX_DEFER
-#define BIVX_DEFER 2
-#endif
 #ifndef BIVX_WSLEEP
 #define BIVX_WSLEEP 16  // s_sleep argument between two polls of a worker's wait in LDS (units of 64 cycles)
 #endif
 #ifndef BIVX_SSLEEP
 #define BIVX_SSLEEP 2   // ... between two passes of the service wavefront that made no progress
 #endif
-#ifndef BIVX_COOP_DEPTH
-#define BIVX_COOP_DEPTH 2   // rounds of coop_mask32 whose loads are in flight together (1: load, wait, evaluate; 2 fits 64 registers)
-#endif
-#ifndef BIVX_PLACE_DEPTH
-#define BIVX_PLACE_DEPTH 2   // rounds of coop_place16 whose loads are in flight together
-#endif
-#ifndef BIVX_EXP
-#define BIVX_EXP 0      // experiments (1, 2, 4: WRONG RESULTS, timing and instruction counts only): 1 no id layout, 2 no id stream-out, 4 no keep slots; 8: coop_mask32 instead of coop_place16 (same results)
-#endif
-constexpr uint32_t kDefer = BIVX_DEFER;  // iterations between counting a slice and writing it out (experiments: 1, 3)
-static_assert(kDefer >= 1 && kDefer <= 3, "deferral depth");
-constexpr uint32_t kPStage = kDefer == 2 ? 320 : (640 / kDefer) & ~3u;   // ids per wavefront stage (there are two: a slice waits two iterations for its base)
+constexpr uint32_t kDefer = 2;     // iterations between counting a slice and writing it out
+constexpr uint32_t kPStage = 320;  // ids per wavefront stage (there are two: a slice waits two iterations for its base)
 #ifndef BIVX_FILL_BLOCKS
 #define BIVX_FILL_BLOCKS 256
 #endif
 constexpr unsigned kFillBlocks = BIVX_FILL_BLOCKS;  // workgroups (of four wavefronts) of k_fill_slices
-constexpr uint32_t kMaxCellForPipe = 64;  // indexes with a fuller directory cell than this stay on k_query_fused
 constexpr uint32_t kPKeep = 8;      // ids kept per query while counting (a wavefront's 64 x 8 slots are its slab too)
 
 // Diagnostic build only (-DBIVX_STAMPS): wall-clock stamps of worker 0, written to a buffer no other code reads.
@@ -108,7 +91,7 @@ struct PipeArgs {
   // in slot order, the CSR is wanted in id order; k_query_pipe_dense and k_fill_slices only). perm[q] = the query's
   // position in the result. The ids are written as always — the batch's lists back to back, in the queries' order — but
   // instead of offsets[q] the kernel leaves src_by_id[perm[q]] = the query's number of ids << kSelfPosBits | where its list
-  // begins (one scattered store per query); k_permute_lists then moves the lists into the result's order.
+  // begins (one scattered store per query); k_permute_lines then moves the lists into the result's order.
   const uint32_t *perm;
   uint64_t *src_by_id;
   uint32_t *unused_;
@@ -190,74 +173,10 @@ __device__ __forceinline__ Win win_of(const WinProbe &p, const uint32_t *table) 
   return Win{dirc_entry_plain(p.ga, ka), dirc_entry_plain(p.gb, kb), p.base, p.fl & 3u};
 }
 
-// Hit mask of a window shorter than 32 slots, read by its own lane (queries in arbitrary order: the windows of a
-// wavefront are scattered over the index). The first sixteen slots — two chunks, up to eight 16-byte loads — leave
-// together, so a window that straddles two chunks costs one round trip, not two; a load is issued only by the lanes whose
-// window reaches its pair (the texture-address unit's time goes by lane, 1.3 lane-loads per cycle and CU measured:
-// tools/ub_gather.hip — clamped duplicates are not free). Evaluation as in slab_mask32, in ascending slot order; the
-// ids of the first KEEP hits go to the lane's keep slots as they are found. Windows of 17..31 slots (a
-// wavefront-uniform branch, rare) take a second round.
-// `wm16`: the window's own bits among the sixteen slots starting at the even slot 2 * p0 — what a predicated-off load
-// left in its registers is evaluated like the rest and masked off. The ids of the hits then go to the lane's keep
-// slots in slot order without a branch: every slot's id is stored at the running position, which advances only past a
-// hit (so a later store overwrites what a non-hit left), and stops at the last keep slot — which therefore holds
-// garbage once KEEP or more hits were found: the caller takes KEEP - 1 ids from the slots in that case.
-template <uint32_t KEEP>
-__device__ __forceinline__ uint32_t eval16(const char *rb, uint32_t p0, uint32_t plast, uint32_t wm16, uint32_t base,
-                                           uint32_t qh, uint32_t ql, uint32_t *keep, uint32_t &kpos) {
-  uint4 r[8];
-#pragma unroll
-  for (uint32_t j = 0; j < 8; ++j)
-#ifdef BIVX_EXP_MAXLOADS  // experiment (wrong results): at most this many record loads per lane
-    if (p0 + j <= plast && j < BIVX_EXP_MAXLOADS) r[j] = *reinterpret_cast<const uint4 *>(rb + ((p0 + j) << 4));
-#else
-    if (p0 + j <= plast) r[j] = *reinterpret_cast<const uint4 *>(rb + ((p0 + j) << 4));
-#endif
-  uint32_t m = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 8; ++j) {
-    const uint32_t rr[2] = {r[j].x, r[j].z};
-#pragma unroll
-    for (uint32_t k = 0; k < 2; ++k) {
-      const uint32_t rl = (rr[k] - base) & 0xFFFFu;
-      m = shift_in_le_ge(m, rl, qh, rl + (rr[k] >> 16), ql);
-    }
-  }
-  m = (__brev(m) >> 16) & wm16;
-#pragma unroll
-  for (uint32_t j = 0; j < 8; ++j) {
-    const uint32_t ii[2] = {r[j].y, r[j].w};
-#pragma unroll
-    for (uint32_t k = 0; k < 2; ++k) {
-      keep[kpos * kWave] = ii[k];  // (slot k of lane l is word k * 64 + l of the wavefront's region: no bank conflict)
-      kpos = min(kpos + ((m >> (2 * j + k)) & 1u), KEEP - 1u);
-    }
-  }
-  return m;
-}
-
-template <uint32_t KEEP>
-__device__ __forceinline__ uint32_t lanes_mask32(const uint2 *rec, const Win &w, bool nonempty, uint32_t lo, uint32_t hi,
-                                                 uint32_t *keep) {
-  const uint32_t al = w.a & ~1u;
-  const uint32_t b = nonempty ? w.b : al;  // (an empty window: no lane-load, no hit)
-  const uint32_t p0 = al >> 1, plast = ((b + 1u) >> 1) - 1u;  // p0 + j <= plast <=> slot al + 2j < b
-  // (the index holds at most 2^28 records when this kernel is chosen: byte offsets fit 32 bits)
-  const char *rb = reinterpret_cast<const char *>(rec);
-  const uint32_t qh = hi - w.base, ql = lo > w.base ? lo - w.base : 0u;
-  const uint32_t wm = ((1u << (b - al)) - 1u) & ~(w.a - al);  // bits [a - al, b - al); a - al is 0 or 1
-  uint32_t kpos = 0;
-  uint32_t m = 0;
-  if (b > al) m = eval16<KEEP>(rb, p0, plast, wm & 0xFFFFu, w.base, qh, ql, keep, kpos);
-  if (__any(b > al + 16u)) {
-    if (b > al + 16u) m |= eval16<KEEP>(rb, p0 + 8u, plast, wm >> 16, w.base, qh, ql, keep, kpos) << 16;
-  }
-  return m;
-}
-
-// The same windows fetched by GROUPS of eight lanes (the default; -DBIVX_NO_COOP keeps lanes_mask32). What bounds the
-// counting of scattered windows is the number of separate requests the vector memory pipeline has to make, not their
-// bytes: with up to eight predicated 16-byte loads per lane a slice is ~350 requests of 16 bytes, and the kernel's time
+// Hit mask of a window shorter than 32 slots (queries in arbitrary order: the windows of a wavefront are scattered over
+// the index), its slots fetched by GROUPS of eight lanes. What bounds the counting of scattered windows is the number of
+// separate requests the vector memory pipeline has to make, not their bytes: a lane that reads its own window makes up to
+// eight predicated 16-byte loads, a slice is then ~350 requests of 16 bytes, and the kernel's time
 // falls 0.323 -> 0.200 ms (config 3) when every lane makes at most ONE of them (wrong results, measured); one workgroup
 // per CU runs as fast as two. Here the eight lanes of a group (lanes 8g .. 8g+7) fetch ONE window together in every
 // round — lane p its p-th pair of records, 128 consecutive bytes per group, 8 windows per load instruction — and the
@@ -265,7 +184,7 @@ __device__ __forceinline__ uint32_t lanes_mask32(const uint2 *rec, const Win &w,
 // instruction instead of 64. The query's parameters travel to the group by ds_swizzle (the LDS crossbar, no memory):
 // three words — first pair | pairs << 27 | q.low bit 16 << 31; the window's base coordinate; q.low | q.high << 16 relative
 // to it (clamped to 17 / 16 bits, which the comparisons cannot tell from the full values). Both records of a lane are
-// evaluated as in eval16; the two ballots carry, in byte g, the hits of group g's even / odd slots: the round's owner
+// evaluated as in slab_mask32; the two ballots carry, in byte g, the hits of group g's even / odd slots: the round's owner
 // keeps its two bytes, and every lane of the group ranks its own hits among them and puts their ids into the OWNER's
 // keep slots (the first KEEP hits). A group does not know where inside its first and last pair the window begins and
 // ends (a is odd, b - al is odd): it reports RAW hits, and the owner — which does — trims the mask and skips what a
@@ -292,7 +211,7 @@ __device__ __forceinline__ uint32_t coop_mask32(const uint2 *rec, uint32_t *keep
   uint32_t *const kbase = keep_of_wave + (lane & 0x38u);  // + rank * 64 + k: slot `rank` of the round's owner
   uint32_t rawA = 0, rawB = 0;  // the owner's bytes of its own round
 
-// A round in two halves, so that the loads of several rounds can be in flight together (BIVX_COOP_DEPTH, default 2: the
+// A round in two halves, so that the loads of two rounds can be in flight together (which fits 64 registers: the
 // round trips of a slice's eight rounds are what a worker's iteration mostly waits for — the kernel is bound by that
 // latency chain, not by instruction issue: profiles/r04_query_kernel_experiments.txt): LOAD fetches the owner's words
 // and issues the group's load, EVAL evaluates what arrived.
@@ -327,14 +246,7 @@ __device__ __forceinline__ uint32_t coop_mask32(const uint2 *rec, uint32_t *keep
     }                                                                                                                 \
   }
 
-// the eight rounds with BIVX_COOP_DEPTH loads in flight
-#if BIVX_COOP_DEPTH == 1
-#define BIVX_COOP_ROUNDS(W0, KEEPIDS, OUTA, OUTB)                                                            \
-  { BIVX_COOP_LOAD(0, W0) BIVX_COOP_EVAL(0, KEEPIDS, OUTA, OUTB) } { BIVX_COOP_LOAD(1, W0) BIVX_COOP_EVAL(1, KEEPIDS, OUTA, OUTB) } \
-  { BIVX_COOP_LOAD(2, W0) BIVX_COOP_EVAL(2, KEEPIDS, OUTA, OUTB) } { BIVX_COOP_LOAD(3, W0) BIVX_COOP_EVAL(3, KEEPIDS, OUTA, OUTB) } \
-  { BIVX_COOP_LOAD(4, W0) BIVX_COOP_EVAL(4, KEEPIDS, OUTA, OUTB) } { BIVX_COOP_LOAD(5, W0) BIVX_COOP_EVAL(5, KEEPIDS, OUTA, OUTB) } \
-  { BIVX_COOP_LOAD(6, W0) BIVX_COOP_EVAL(6, KEEPIDS, OUTA, OUTB) } { BIVX_COOP_LOAD(7, W0) BIVX_COOP_EVAL(7, KEEPIDS, OUTA, OUTB) }
-#elif BIVX_COOP_DEPTH == 2
+// the eight rounds, two rounds' loads in flight
 #define BIVX_COOP_ROUNDS(W0, KEEPIDS, OUTA, OUTB)                                                            \
   {                                                                                                          \
     BIVX_COOP_LOAD(0, W0) BIVX_COOP_LOAD(1, W0) BIVX_COOP_EVAL(0, KEEPIDS, OUTA, OUTB)                       \
@@ -343,30 +255,10 @@ __device__ __forceinline__ uint32_t coop_mask32(const uint2 *rec, uint32_t *keep
     BIVX_COOP_LOAD(6, W0) BIVX_COOP_EVAL(5, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(7, W0) BIVX_COOP_EVAL(6, KEEPIDS, OUTA, OUTB) \
     BIVX_COOP_EVAL(7, KEEPIDS, OUTA, OUTB)                                                                   \
   }
-#elif BIVX_COOP_DEPTH == 3
-#define BIVX_COOP_ROUNDS(W0, KEEPIDS, OUTA, OUTB)                                                            \
-  {                                                                                                          \
-    BIVX_COOP_LOAD(0, W0) BIVX_COOP_LOAD(1, W0) BIVX_COOP_LOAD(2, W0) BIVX_COOP_EVAL(0, KEEPIDS, OUTA, OUTB) \
-    BIVX_COOP_LOAD(3, W0) BIVX_COOP_EVAL(1, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(4, W0) BIVX_COOP_EVAL(2, KEEPIDS, OUTA, OUTB) \
-    BIVX_COOP_LOAD(5, W0) BIVX_COOP_EVAL(3, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(6, W0) BIVX_COOP_EVAL(4, KEEPIDS, OUTA, OUTB) \
-    BIVX_COOP_LOAD(7, W0) BIVX_COOP_EVAL(5, KEEPIDS, OUTA, OUTB) BIVX_COOP_EVAL(6, KEEPIDS, OUTA, OUTB)      \
-    BIVX_COOP_EVAL(7, KEEPIDS, OUTA, OUTB)                                                                   \
-  }
-#else  // 4
-#define BIVX_COOP_ROUNDS(W0, KEEPIDS, OUTA, OUTB)                                                            \
-  {                                                                                                          \
-    BIVX_COOP_LOAD(0, W0) BIVX_COOP_LOAD(1, W0) BIVX_COOP_LOAD(2, W0) BIVX_COOP_LOAD(3, W0)                  \
-    BIVX_COOP_EVAL(0, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(4, W0) BIVX_COOP_EVAL(1, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(5, W0) \
-    BIVX_COOP_EVAL(2, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(6, W0) BIVX_COOP_EVAL(3, KEEPIDS, OUTA, OUTB) BIVX_COOP_LOAD(7, W0) \
-    BIVX_COOP_EVAL(4, KEEPIDS, OUTA, OUTB) BIVX_COOP_EVAL(5, KEEPIDS, OUTA, OUTB)                            \
-    BIVX_COOP_EVAL(6, KEEPIDS, OUTA, OUTB) BIVX_COOP_EVAL(7, KEEPIDS, OUTA, OUTB)                            \
-  }
-#endif
 
   {
     const uint32_t w0 = (al >> 1) | (npairs < 8u ? npairs : 8u) << 27 | (ql >> 16) << 31;
-    constexpr bool kk = (BIVX_EXP & 4) == 0;
-    BIVX_COOP_ROUNDS(w0, kk, rawA, rawB)
+    BIVX_COOP_ROUNDS(w0, true, rawA, rawB)
   }
   const uint32_t raw = spread8(rawA) | spread8(rawB) << 1;
   const uint32_t wm = ((1u << n) - 1u) & ~(w.a - al);  // the window's own bits: [a - al, n); a - al is 0 or 1
@@ -475,24 +367,12 @@ __device__ __forceinline__ uint32_t coop_place16(const uint2 *rec, uint32_t *out
     wpos += nh;                                                                                                       \
   }
 
-  {  // (BIVX_PLACE_DEPTH rounds' loads in flight: 2 by default)
-#if BIVX_PLACE_DEPTH == 4
-    BIVX_PLACE_LOAD(0) BIVX_PLACE_LOAD(1) BIVX_PLACE_LOAD(2) BIVX_PLACE_LOAD(3) BIVX_PLACE_EVAL(0)
-    BIVX_PLACE_LOAD(4) BIVX_PLACE_EVAL(1) BIVX_PLACE_LOAD(5) BIVX_PLACE_EVAL(2)
-    BIVX_PLACE_LOAD(6) BIVX_PLACE_EVAL(3) BIVX_PLACE_LOAD(7) BIVX_PLACE_EVAL(4)
-    BIVX_PLACE_EVAL(5) BIVX_PLACE_EVAL(6) BIVX_PLACE_EVAL(7)
-#elif BIVX_PLACE_DEPTH == 3
-    BIVX_PLACE_LOAD(0) BIVX_PLACE_LOAD(1) BIVX_PLACE_LOAD(2) BIVX_PLACE_EVAL(0)
-    BIVX_PLACE_LOAD(3) BIVX_PLACE_EVAL(1) BIVX_PLACE_LOAD(4) BIVX_PLACE_EVAL(2)
-    BIVX_PLACE_LOAD(5) BIVX_PLACE_EVAL(3) BIVX_PLACE_LOAD(6) BIVX_PLACE_EVAL(4)
-    BIVX_PLACE_LOAD(7) BIVX_PLACE_EVAL(5) BIVX_PLACE_EVAL(6) BIVX_PLACE_EVAL(7)
-#else
+  {  // (two rounds' loads in flight)
     BIVX_PLACE_LOAD(0) BIVX_PLACE_LOAD(1) BIVX_PLACE_EVAL(0)
     BIVX_PLACE_LOAD(2) BIVX_PLACE_EVAL(1) BIVX_PLACE_LOAD(3) BIVX_PLACE_EVAL(2)
     BIVX_PLACE_LOAD(4) BIVX_PLACE_EVAL(3) BIVX_PLACE_LOAD(5) BIVX_PLACE_EVAL(4)
     BIVX_PLACE_LOAD(6) BIVX_PLACE_EVAL(5) BIVX_PLACE_LOAD(7) BIVX_PLACE_EVAL(6)
     BIVX_PLACE_EVAL(7)
-#endif
   }
 #undef BIVX_PLACE_LOAD
 #undef BIVX_PLACE_EVAL
@@ -539,11 +419,7 @@ __device__ __forceinline__ void pipe_service_wave(kargs_t ka, TileSlot *s_slot, 
     // ---- a ticket ----
     if (drawing && drawn - swept < kRing) {
       bool want = drawn == 0;
-#ifdef BIVX_TICKET_EARLY   // experiment: a counting phase ahead (when that many workers have begun the tile before; NW = all)
-      if (!want) want = drawn == 1 || lds_load(&s_slot[(drawn - 2) % kRing].arrived) >= (uint32_t)(BIVX_TICKET_EARLY);
-#else
       if (!want) want = lds_load(&s_slot[(drawn - 1) % kRing].arrived) != 0;
-#endif
       TileSlot &sl = s_slot[drawn % kRing];
       // (the slot's last user was iteration drawn - kRing: swept, but every worker must also be through with it)
       if (want && (drawn < kRing || lds_load(&sl.flushed) == (uint32_t)NW)) {
@@ -785,7 +661,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
                             (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(wpos0 >> 32)) << 32;
         uint32_t *const out = p->a.hits + wp;
         const uint32_t lim = cap > wp ? (cap - wp < pd.wtotal ? (uint32_t)(cap - wp) : pd.wtotal) : 0u;
-        if (!(BIVX_EXP & 2)) stage_to_output(stage, out, lim, tid() & (kWave - 1));
+        stage_to_output(stage, out, lim, tid() & (kWave - 1));
       }
     } else {
       // an unstaged slice kept (list offset, count) per lane in its stage; its ids are k_fill_slices' business
@@ -851,7 +727,7 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
         path = nin >= kSlabMinLanes && nin == nne ? 1 : 2;
         // scattered windows of at most sixteen slots (and no query that begins 64 K above its window's base: low > high
         // queries can): the ids go straight to their places (coop_place16)
-        if (path == 2 && (BIVX_EXP & 8) == 0 &&
+        if (path == 2 &&
             !__any(nonempty && (wn.b - al > 16u || (qlo > wn.base && qlo - wn.base > 0xFFFFu) || (al >> 1) >= (1u << 26))))
           path = 3;
       }
@@ -869,13 +745,8 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
         wtotal = coop_place16(fresh(ka)->v.rec, reinterpret_cast<uint32_t *>(slab_of_wave()), wn, nonempty, qlo, qhi,
                               tid() & (kWave - 1), !no_ids, cnt, loff);
       } else if (path == 2) {
-#ifdef BIVX_NO_COOP
-        m32 = lanes_mask32<kPKeep>(fresh(ka)->v.rec, wn, nonempty, qlo, qhi, kept_slots());
-        kinfo = 0xFFFFFFFFu;
-#else
         m32 = coop_mask32<kPKeep>(fresh(ka)->v.rec, reinterpret_cast<uint32_t *>(slab_of_wave()), wn, nonempty, qlo, qhi,
                                   tid() & (kWave - 1), kinfo);
-#endif
         cnt = (uint32_t)__popc(m32);
       } else {
         kargs_t p = fresh(ka);
@@ -966,7 +837,6 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
       stage[3 * lane] = (uint32_t)lpos64;
       stage[3 * lane + 1] = (uint32_t)(lpos64 >> 32);
       stage[3 * lane + 2] = cnt;
-    } else if ((BIVX_EXP & 1) != 0) {
     } else if (!no_ids && path == 1) {  // the ids are in the wavefront's slab
       const uint2 *s2 = reinterpret_cast<const uint2 *>(slab_of_wave()) + ((qw_a & ~1u) - lbase);
       uint32_t *dst = stage + loff;
@@ -981,13 +851,8 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe(IndexView v_in, Pip
       for (uint32_t i = tid() & (kWave - 1); i < (wtotal + 3u) >> 2; i += kWave) dst[i] = src[i];
     } else if (!no_ids && path == 2) {  // the first kPKeep ids are in the lane's keep slots; a longer list re-reads the rest
       uint32_t *dst = stage + loff;
-#ifdef BIVX_NO_COOP
-      const uint32_t *kslots = kept_slots();
-      const uint32_t nk = cnt < kPKeep ? cnt : kPKeep - 1u;  // (the last slot is only good while it was not the limit)
-#else
       const uint32_t *kslots = kept_slots() + (kinfo & 1u) * kWave;  // (a false first hit sits in slot 0)
       const uint32_t nk = cnt < (kinfo >> 1) ? cnt : kinfo >> 1;
-#endif
       for (uint32_t k = 0; k < nk; ++k) {
         dst[k] = kslots[k * kWave];
         m32 &= m32 - 1u;
@@ -1393,17 +1258,10 @@ __global__ __launch_bounds__(kPThreads, 8) void k_query_pipe_dense(IndexView v_i
 // where this runs 0.136 / 0.493; 256 threads 0.159 / 0.505.
 constexpr int kMsThreads = 512;
 constexpr int kMsWorkers = kMsThreads / kWave - 1;
-constexpr uint32_t kMsTile = kMsWorkers * kWave;
-#ifndef BIVX_MS_DEFER
-#define BIVX_MS_DEFER 2   // iterations a counted slice waits for its place in the output (1: experiment — one pending slice, twice the keep slots)
-#endif
-constexpr uint32_t kMsDefer = BIVX_MS_DEFER;
-constexpr uint32_t kMsKeepN = 32 / kMsDefer;                     // ids a lane keeps while its slice is pending — on average: see ms_keep_word
-#ifdef BIVX_MS_NOKEEP
-constexpr uint32_t kMsKeepWords = 0;
-#else
+static_assert(kMsWorkers * kWave == kMsTile, "query_route.h plans launches of kMsTile queries per tile");
+constexpr uint32_t kMsDefer = 2;                                // iterations a counted slice waits for its place in the output
+constexpr uint32_t kMsKeepN = 16;                                // ids a lane keeps while its slice is pending — on average: see ms_keep_word
 constexpr uint32_t kMsKeepWords = kMsKeepN * kWave;              // ... a wavefront's keep slots, one pending slice
-#endif
 #ifndef BIVX_MS_UNFIT_RUN
 #define BIVX_MS_UNFIT_RUN 2
 #endif
@@ -1422,7 +1280,6 @@ constexpr uint32_t kMsStage = kMsDefer * kMsKeepWords + kMsBuf;  // a wavefront'
 constexpr uint32_t kMsOwnTrip = BIVX_MS_OWN_TRIP;                // slots of its own window a lane evaluates per trip
 constexpr uint32_t kMsOwnSlots = BIVX_MS_OWN;                    // a segment whose windows all end within that many slots of their
                                                                  // first even slot: every lane evaluates its own (0: never)
-constexpr uint32_t kMsGroupMax = 1024;                           // slots of the longest window a group of lanes walks
 
 // Every lane's hits over all its segments, in index order (segment, slot), by GROUPS of eight lanes, as coop_mask32 does it
 // for the short windows of k_query_pipe: in step j of a round the group fetches sixteen slots — one 128-byte line of
@@ -1455,11 +1312,6 @@ __device__ __forceinline__ uint32_t ms_keep_word(uint32_t i, uint32_t lane) {
 // the wavefront's 64 x kMsKeepN words, ms_keep_word; at most 2 x kMsKeepN per lane are written); kMsEmit — the ids go to
 // stage[lpos ..) (the output itself; positions from `limit` on are not written).
 constexpr int kMsCount = 0, kMsKeep = 1, kMsEmit = 2;
-#ifdef BIVX_EXP_NOSTORE  // experiment (wrong results): the second walk without its stores
-#define BIVX_EXP_STORE(c) ((c) && limit == 0x12345u)
-#else
-#define BIVX_EXP_STORE(c) (c)
-#endif
 template <int MODE, bool F>
 __device__ __forceinline__ uint32_t group_scan(kargs_t ka, const SegDesc *segs, const Query &q, bool active, uint32_t *stage,
                                                uint32_t lpos, uint32_t limit, uint32_t lane, uint32_t *tab, bool &too_long) {
@@ -1568,8 +1420,8 @@ __device__ __forceinline__ uint32_t group_scan(kargs_t ka, const SegDesc *segs, 
               if (fb && atB < 2u * kMsKeepN) stage[ms_keep_word(atB, lane)] = idb;
             } else {
               char *const ob = reinterpret_cast<char *>(stage);
-              if (BIVX_EXP_STORE(fa && atA < limit)) *reinterpret_cast<uint32_t *>(ob + (atA << 2)) = ida;
-              if (BIVX_EXP_STORE(fb && atB < limit)) *reinterpret_cast<uint32_t *>(ob + (atB << 2)) = idb;
+              if (fa && atA < limit) *reinterpret_cast<uint32_t *>(ob + (atA << 2)) = ida;
+              if (fb && atB < limit) *reinterpret_cast<uint32_t *>(ob + (atB << 2)) = idb;
             }
           }
           acc += (fa ? 1u : 0u) + (fb ? 1u : 0u);
@@ -1635,8 +1487,8 @@ __device__ __forceinline__ uint32_t group_scan(kargs_t ka, const SegDesc *segs, 
         if (mineB && at + mineA < 2u * kMsKeepN) stage[ms_keep_word(at + mineA, gsh | (J))] = idb;             \
       } else { /* (a slice has fewer than 2^28 ids: 32-bit byte offsets from the slice's first output position) */ \
         char *const ob = reinterpret_cast<char *>(stage);                                                      \
-        if (BIVX_EXP_STORE(mineA && at < limit)) *reinterpret_cast<uint32_t *>(ob + (at << 2)) = ida;          \
-        if (BIVX_EXP_STORE(mineB && at + mineA < limit)) *reinterpret_cast<uint32_t *>(ob + ((at + mineA) << 2)) = idb; \
+        if (mineA && at < limit) *reinterpret_cast<uint32_t *>(ob + (at << 2)) = ida;          \
+        if (mineB && at + mineA < limit) *reinterpret_cast<uint32_t *>(ob + ((at + mineA) << 2)) = idb; \
       }                                                                                                        \
     }                                                                                                          \
     if (p == (J)) acc += (uint32_t)__popc(bA) + (uint32_t)__popc(bB);                                          \
@@ -1747,7 +1599,7 @@ __global__ __launch_bounds__(kMsThreads, BIVX_MS_WAVES) void k_query_pipe_ms(Ind
       const uint32_t room = cap > wp ? (cap - wp < 0xFFFFFFFFull ? (uint32_t)(cap - wp) : 0xFFFFFFFFu) : 0u;
       if (pd.kept) {
         // out of the keep slots: kMsBuf ids at a time are lined up as they sit in the output and leave in whole lines
-        const uint32_t *const keep = s_stage[wave] + (kMsDefer == 2 ? (j & 1u) * kMsKeepWords : 0u);
+        const uint32_t *const keep = s_stage[wave] + (j & 1u) * kMsKeepWords;
         uint32_t *const buf = s_stage[wave] + kMsDefer * kMsKeepWords;
         for (uint32_t r0 = 0; r0 < pd.wtotal; r0 += kMsBuf) {
           const uint32_t i0 = r0 > loff ? r0 - loff : 0u;                                         // the lane's ids i0 .. i1-1 are in
@@ -1774,25 +1626,16 @@ __global__ __launch_bounds__(kMsThreads, BIVX_MS_WAVES) void k_query_pipe_ms(Ind
   lds_wait_eq(&s_slot[0].gen_ticket, 1u);
   uint32_t tile = __builtin_amdgcn_readfirstlane(s_slot[0].tile);
   Query qy = query_of(tile);
-#ifdef BIVX_MS_NOKEEP  // experiment: every slice is walked twice, no keep slots in use
-  bool keep_mode = false;
-#else
   bool keep_mode = true;
   uint32_t unfit_run = 0;  // slices in a row that had a list beyond the keep slots
-#endif
 
   for (uint32_t it = 0;; ++it) {
     const bool live = tile < A(ntiles);
     // the slice counted two iterations ago goes out FIRST: its keep slots are the ones this iteration's slice fills
-    if (kMsDefer == 2) {
-      if (pb.have) flush(pb, it - 2);
-      if (!live) {
-        if (pa.have) flush(pa, it - 1);
-        break;
-      }
-    } else {
+    if (pb.have) flush(pb, it - 2);
+    if (!live) {
       if (pa.have) flush(pa, it - 1);
-      if (!live) break;
+      break;
     }
     bool too_long;
     uint32_t cnt;
@@ -1802,7 +1645,7 @@ __global__ __launch_bounds__(kMsThreads, BIVX_MS_WAVES) void k_query_pipe_ms(Ind
     if (no_ids)
       cnt = group_scan<kMsCount, F>(ka, segs, qy, true, nullptr, 0u, 0u, (uint32_t)lane, s_stage[wave] + kMsDefer * kMsKeepWords, too_long);
     else
-      cnt = group_scan<kMsKeep, F>(ka, segs, qy, true, s_stage[wave] + (kMsDefer == 2 ? (it & 1u) * kMsKeepWords : 0u), 0u, 0u, (uint32_t)lane,
+      cnt = group_scan<kMsKeep, F>(ka, segs, qy, true, s_stage[wave] + (it & 1u) * kMsKeepWords, 0u, 0u, (uint32_t)lane,
                                    s_stage[wave] + kMsDefer * kMsKeepWords, too_long);
     if (too_long) {
       kargs_t p = fresh(ka);
@@ -1837,14 +1680,12 @@ __global__ __launch_bounds__(kMsThreads, BIVX_MS_WAVES) void k_query_pipe_ms(Ind
     const uint32_t pair_cnt = cnt + (uint32_t)__builtin_amdgcn_ds_swizzle((int)cnt, 0x041F);  // (xor 1: the neighbour's count)
     const bool fits = !general && !__any(pair_cnt > 2u * kMsKeepN);
     const bool kept = fits && !no_ids;
-#ifndef BIVX_MS_NOKEEP
     // (two slices in a row with a list beyond the keep slots before the first walk stops keeping ids: with 7.6 ids per query
     // 18 % of the slices have such a list, and giving up keeping after every one of them made a third of all slices walk twice)
     if (!general) {
       unfit_run = fits ? 0u : unfit_run + 1u;
       keep_mode = unfit_run < BIVX_MS_UNFIT_RUN;
     }
-#endif
     uint32_t wtotal = wave_last(incl);
     uint64_t wt64 = wtotal, lpos64 = incl - cnt;
     if (huge) {
@@ -1954,75 +1795,11 @@ __global__ __launch_bounds__(kQThreads) void k_fill_slices(IndexView v, PipeArgs
 
 }  // namespace
 
-// true if the pipelined kernel handled the launch (the caller falls back to k_query_fused otherwise)
-static int mode_forced() {
-  const char *env = std::getenv("BIVX_PIPE");
-  return env ? std::atoi(env) : 1;
-}
-
-bool pipe_eligible(const IndexView &v, size_t q, uint64_t cap, bool sort_ids, bool unordered) {
-  // (begin / count output: the ordered CSR is a valid answer, and since the pipelined kernel it is the faster one —
-  // config 3 0.33 against 0.35 ms; one launch only, there is no entry q_end to chain launches through)
-  // Only for large batches: at 1 M queries k_query_fused<U>, whose tiles wait for nobody, takes 43 us (22 position-sorted)
-  // against 48 (32) here.
-  if (unordered && (sort_ids || q > (size_t)kFMaxTiles * kPTile || (q < ((size_t)4 << 20) && mode_forced() != 2))) return false;
-  // BIVX_PIPE: 0 = never, 1 = when eligible (default), 2 = also for small batches (tests)
-  const char *env = std::getenv("BIVX_PIPE");
-  const int mode = env ? std::atoi(env) : 1;
-  if (!mode || v.flt_kind != BIVX_FILTER_NONE || v.max_segs > 1 || !fits_lds(v)) return false;
-  if (v.nslots > (1u << 28)) return false;  // (32-bit byte offsets into the records, lanes_mask32)
-  // Positional hotspots (thousands of intervals starting inside one directory cell) make single slices take hundreds of
-  // microseconds; a tile here waits for all fifteen of its slices, k_query_fused's tiles wait for nobody but their
-  // predecessors' totals (tools/clustered_bench.py, zero-capacity count: 1.32 ms here, 0.78 there)
-  if (v.max_cell > kMaxCellForPipe && mode != 2) return false;
-  // a pipeline has to fill and drain: below about 0.7 M queries (1.4 tiles per resident workgroup) k_query_fused is
-  // the faster one (0.25 M: 19.7 against 23.7 us, 0.5 M: 32 / 35, 0.75 M: 45 / 43, 1 M: 54 / 49, 1.3 M: 70 / 60)
-  if (q < (size_t)768 * 1024 && mode != 2) return false;
-  // few ids per query: a wavefront's 64 lists must fit its stage (the capacity is the only bound the host has)
-  return cap <= (uint64_t)6 * q;
-}
-
-// Many ids per query (more than the stages hold): the regenerating form of the pipeline, for position-sorted batches
-// (the kernel itself returns at once when k_probe_order found the batch unsorted; the caller launches k_query_fused
-// behind it with the opposite condition).
-bool pipe_dense_eligible(const IndexView &v, size_t q, uint64_t cap, bool sort_ids, bool unordered) {
-  (void)sort_ids;  // (ascending ids: k_sort_hits orders the CSR afterwards, whichever kernel wrote it)
-  const char *env = std::getenv("BIVX_PIPE");
-  const int mode = env ? std::atoi(env) : 1;
-  if (!mode || unordered || v.flt_kind != BIVX_FILTER_NONE || v.max_segs > 1 || !fits_lds(v)) return false;
-  if (v.nslots > (1u << 28) || (v.max_cell > kMaxCellForPipe && mode != 2)) return false;
-  if (q < (size_t)4 * 512 * kPTile && mode != 2) return false;
-  return cap > (uint64_t)6 * q;
-}
-
-// What k_query_pipe leaves out — several segments per chromosome, a fused filter — in index order, canonical CSR
-// (ascending ids: k_sort_hits behind it, as behind k_query_fused).
-bool pipe_ms_eligible(const IndexView &v, size_t q, uint64_t cap, bool unordered) {
-  const char *env = std::getenv("BIVX_PIPE");
-  const int mode = env ? std::atoi(env) : 1;
-  if (const char *e = std::getenv("BIVX_PIPE_MS"))  // (0: never — tests compare the two kernels)
-    if (std::atoi(e) == 0) return false;
-  if (!mode || unordered || !fits_lds(v)) return false;
-  if (q < (size_t)768 * 1024 && mode != 2) return false;
-  {  // (se[] and rec[] in one block, 32-bit byte offsets from se[] into both; ids 8 bytes per pair)
-    const ptrdiff_t delta = reinterpret_cast<const char *>(v.rec) - reinterpret_cast<const char *>(v.se);
-    if (v.nslots > (1u << 27) || delta < 0 || (uint64_t)delta + ((uint64_t)v.nslots + 2) * 8 > 0xFFFFFFFFull) return false;
-  }
-  // (positional hotspots: windows beyond kMsGroupMax slots go through the general enumeration twice here)
-  if ((v.max_cell > kMsGroupMax / 4 || v.max_window > kMsGroupMax / 2) && mode != 2) return false;
-  // (many ids per query on ONE length class, queries in any order: k_query_fused is the faster one — config 5 in
-  // generation order 7.7 ms against 8.5 here; tests send it here with BIVX_PIPE=2)
-  return v.max_segs > 1 || v.flt_kind != BIVX_FILTER_NONE || (mode == 2 && cap > (uint64_t)6 * q);
-}
-
-size_t pipe_queries_per_launch() { return (size_t)kFMaxTiles * kPTile; }
 static_assert((uint64_t)kFMaxTiles * kPTile < (1ull << (64 - kSelfPosBits)),
               "bivx_self_overlaps_dev keeps a list's length (at most the launch's intervals) above kSelfPosBits of one word");
-size_t pipe_ms_queries_per_launch() { return (size_t)kFMaxTiles * kMsTile; }
 
 // Compute units of the calling thread's current device, looked up once per device and process (a launch used to ask the
-// runtime every time: hipGetDevice + hipDeviceGetAttribute are microseconds on the path of a 40 us call). The environment
-// knobs below stay per launch: tests switch them between calls.
+// runtime every time: hipGetDevice + hipDeviceGetAttribute are microseconds on the path of a 40 us call).
 static unsigned cus_of_current_device() {
   static std::atomic<unsigned> cache[64];
   int dev = 0;
@@ -2036,23 +1813,22 @@ static unsigned cus_of_current_device() {
   return c;
 }
 
+// Workgroups of a pipelined kernel's launch: two are resident per CU (k_query_pipe(_dense): 1024 threads, 64 VGPRs, 71 KiB of
+// LDS each; k_query_pipe_ms: 512 threads, 128 registers, 79 KB), unless BIVX_PIPE_WGS says otherwise.
+static dim3 pipe_grid(unsigned tiles, const RouteKnobs &k) {
+  const unsigned wgs = k.wgs ? k.wgs : 2u * cus_of_current_device();
+  return dim3(tiles < wgs ? tiles : wgs);
+}
+
 int launch_query_pipe_ms(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                          size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                         int flags, uint32_t skip_seq, hipStream_t s) {
+                         int flags, uint32_t skip_seq, const RouteKnobs &knobs, hipStream_t s) {
   const unsigned tiles = (unsigned)((q1 - q0 + kMsTile - 1) / kMsTile);
-  unsigned wgs = 512;
-  {
-    wgs = 2u * cus_of_current_device();  // two workgroups of 512 threads per CU: 128 registers, 79 KB of LDS each
-    if (const char *e = std::getenv("BIVX_PIPE_WGS")) {
-      const long w = std::atol(e);
-      if (w >= 1 && w <= 65536) wgs = (unsigned)w;
-    }
-  }
   // (seq: launched behind k_query_pipe_dense, which did the launch's work if the order probe left this number)
   PipeArgs a{d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, tiles, flags, skip_seq, nullptr, nullptr,
              nullptr, nullptr, nullptr, (uint32_t)(reinterpret_cast<const char *>(v.rec) - reinterpret_cast<const char *>(v.se)),
              kMsTile};
-  const dim3 grid(tiles < wgs ? tiles : wgs);
+  const dim3 grid = pipe_grid(tiles, knobs);
   if (v.flt_kind != BIVX_FILTER_NONE) {
     hipLaunchKernelGGL(k_query_pipe_ms<true>, grid, dim3(kMsThreads), 0, s, v, a);
     if (cap != 0) hipLaunchKernelGGL((k_fill_slices<false, true>), dim3(kFillBlocks), dim3(kQThreads), 0, s, v, a);
@@ -2066,22 +1842,15 @@ int launch_query_pipe_ms(const IndexView &v, const uint32_t *d_qchrom, const uin
 
 int launch_query_pipe(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                       size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                      int flags, uint32_t sort_seq, uint32_t *d_counts, uint64_t *d_total, hipStream_t s) {
+                      int flags, uint32_t sort_seq, uint32_t *d_counts, uint64_t *d_total, const RouteKnobs &knobs,
+                      hipStream_t s) {
   const unsigned tiles = (unsigned)((q1 - q0 + kPTile - 1) / kPTile);
-  unsigned wgs = 512;
-  {
-    wgs = 2u * cus_of_current_device();  // two workgroups of 1024 threads are resident per CU (64 VGPRs, 71 KiB of LDS)
-    if (const char *e = std::getenv("BIVX_PIPE_WGS")) {  // tuning / test knob
-      const long w = std::atol(e);
-      if (w >= 1 && w <= 65536) wgs = (unsigned)w;
-    }
-  }
   PipeArgs a{d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, tiles, flags, sort_seq, d_counts, d_total,
              nullptr, nullptr, nullptr, 0u, kPTile};
   if (sort_seq)
-    hipLaunchKernelGGL(k_query_pipe<true>, dim3(tiles < wgs ? tiles : wgs), dim3(kPThreads), 0, s, v, a);
+    hipLaunchKernelGGL(k_query_pipe<true>, pipe_grid(tiles, knobs), dim3(kPThreads), 0, s, v, a);
   else
-    hipLaunchKernelGGL(k_query_pipe<false>, dim3(tiles < wgs ? tiles : wgs), dim3(kPThreads), 0, s, v, a);
+    hipLaunchKernelGGL(k_query_pipe<false>, pipe_grid(tiles, knobs), dim3(kPThreads), 0, s, v, a);
   if (cap == 0) {
     // a pure count: nothing is listed, nothing to fill in (the launch, empty as it usually is, costs 4.8 us)
   } else if (sort_seq) {
@@ -2095,103 +1864,22 @@ int launch_query_pipe(const IndexView &v, const uint32_t *d_qchrom, const uint32
 
 int launch_query_pipe_dense(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                             size_t q0, size_t q1, uint64_t *d_offsets, uint32_t *d_hits, uint64_t cap, uint64_t *ws,
-                            int flags, uint32_t seq, hipStream_t s) {
+                            int flags, uint32_t seq, const RouteKnobs &knobs, hipStream_t s) {
   const unsigned tiles = (unsigned)((q1 - q0 + kPTile - 1) / kPTile);
-  unsigned wgs = 512;
-  {
-    wgs = 2u * cus_of_current_device();
-    if (const char *e = std::getenv("BIVX_PIPE_WGS")) {
-      const long w = std::atol(e);
-      if (w >= 1 && w <= 65536) wgs = (unsigned)w;
-    }
-  }
   PipeArgs a{d_qchrom, d_qlow, d_qhigh, q0, q1, d_offsets, d_hits, cap, ws, tiles, flags, seq, nullptr, nullptr,
              nullptr, nullptr, nullptr, 0u, kPTile};
   hipLaunchKernelGGL(k_probe_order, dim3(1), dim3(256), 0, s, d_qchrom, d_qlow, q0, q1, ws, seq);
-  hipLaunchKernelGGL(k_query_pipe_dense, dim3(tiles < wgs ? tiles : wgs), dim3(kPThreads), 0, s, v, a);
+  hipLaunchKernelGGL(k_query_pipe_dense, pipe_grid(tiles, knobs), dim3(kPThreads), 0, s, v, a);
   a.seq = 0;  // (k_fill_slices: index order)
   if (cap != 0) hipLaunchKernelGGL(k_fill_slices<false>, dim3(kFillBlocks), dim3(kQThreads), 0, s, v, a);
   BIVX_HIP(hipGetLastError());
   return 0;
 }
 
-// The index overlapped with itself (bivx_self_overlaps_dev): the queries are the index's own intervals in SLOT order —
-// position-sorted by construction, which is what k_query_pipe_dense is for — and the result is wanted in id order:
-// perm = the slots' ids. The kernel writes the lists back to back in slot order into d_tmp_hits and leaves, per id, the
-// list's length and where it begins; offsets are a scan of the lengths; k_permute_lists gathers the lists into place.
-// (Writing every list straight to its place from the slot-order pass was tried first: 50 M lists of ~68 bytes at random
-// places of a 3.4 GB buffer are partial-line writes the memory side has to read-modify-write: 6.1 ms for that pass at
-// config 5. Random READS of the same lists run at the gather rate, and the writes are a stream.)
-bool self_overlaps_eligible(const IndexView &v, size_t n) {
-  const char *env = std::getenv("BIVX_PIPE");
-  const int mode = env ? std::atoi(env) : 1;
-  if (!mode || v.flt_kind != BIVX_FILTER_NONE || v.max_segs > 1 || !fits_lds(v)) return false;
-  if (v.nslots > (1u << 28) || v.max_cell > kMaxCellForPipe) return false;
-  if (n > pipe_queries_per_launch()) return false;  // (one launch: nothing chains output positions across launches)
-  return n >= (size_t)64 * kPTile || mode == 2;
-}
-
-// result list i = d_tmp[src[i] .. src[i] + (offsets[i + 1] - offsets[i])), written to d_hits[offsets[i] ..). A wavefront
-// takes 64 consecutive lists — one contiguous piece of the output — and every lane one output element at a time: the
-// element's list is found by bisection of the 64 list ends in LDS, its source is a gather, the stores are a stream.
-__global__ __launch_bounds__(kQThreads) void k_permute_lists(const uint64_t *__restrict__ offsets,
-                                                             const uint64_t *__restrict__ src, const uint32_t *__restrict__ tmp,
-                                                             uint32_t *__restrict__ hits, size_t n, uint64_t cap) {
-  __shared__ uint32_t s_end[kQWaves][kWave];
-  __shared__ uint64_t s_src[kQWaves][kWave];
-  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const size_t i = (size_t)blockIdx.x * kQThreads + threadIdx.x;
-  const uint64_t o0 = offsets[i < n ? i : n], o1 = offsets[i < n ? i + 1 : n];
-  const uint64_t wb = __shfl((unsigned long long)o0, 0, kWave);  // the wavefront's piece of the output: [wb, we)
-  const uint64_t we = __shfl((unsigned long long)o1, kWave - 1, kWave);
-  if (we - wb > 0xFFFFFFFFull) {  // (more than 2^32 ids in 64 lists: every lane copies its own)
-    if (i < n)
-      for (uint64_t k = 0; k < o1 - o0; ++k)
-        if (o0 + k < cap) hits[o0 + k] = tmp[(src[i] & kSelfPosMask) + k];
-    return;
-  }
-  s_end[wave][lane] = (uint32_t)(o1 - wb);
-  s_src[wave][lane] = i < n ? (src[i] & kSelfPosMask) - (o0 - wb) : 0ull;  // source of the list's first element, minus its place in the piece
-  wave_sync_lds();
-  const uint32_t total = (uint32_t)(we - wb);
-  // every lane one output element of four consecutive rows of 64 per trip: four bisections, then four gathers in flight,
-  // then four row stores (each row a 256-byte stream). (One row per trip: 3.3 ms at config 5; four consecutive
-  // elements per lane moved as 16 bytes — unaligned gathers and stores — 4.9.)
-  constexpr uint32_t kRowsPerTrip = 4;
-  for (uint32_t e0 = lane; e0 < total; e0 += kWave * kRowsPerTrip) {
-    uint32_t owner[kRowsPerTrip];
-#pragma unroll
-    for (uint32_t r = 0; r < kRowsPerTrip; ++r) {
-      const uint32_t e = e0 + r * kWave;
-      uint32_t lo = 0, hi = kWave - 1;  // first list whose end is beyond e
-#pragma unroll
-      for (int step = 0; step < 6; ++step) {  // (64 lists: six halvings, branch-free)
-        const uint32_t m = (lo + hi) >> 1;
-        const bool right = s_end[wave][m] <= e;
-        lo = right ? m + 1 : lo;
-        hi = right ? hi : m;
-      }
-      owner[r] = lo < kWave ? lo : kWave - 1;
-    }
-    uint32_t x[kRowsPerTrip];
-    bool ok[kRowsPerTrip];
-#pragma unroll
-    for (uint32_t r = 0; r < kRowsPerTrip; ++r) {
-      const uint32_t e = e0 + r * kWave;
-      const uint64_t sp = s_src[wave][owner[r]] + e;
-      ok[r] = e < total && wb + e < cap && sp < cap;
-      x[r] = ok[r] ? stream_load(tmp + sp) : 0u;
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < kRowsPerTrip; ++r)
-      if (ok[r]) stream_store(hits + wb + e0 + r * kWave, x[r]);
-  }
-}
-
-// The same, a line at a time (the default; k_permute_lists keeps wavefronts with very long lists). Random 128-byte lines
-// come out of HBM at 45-50 G per second when a group of eight lanes asks for one (tools/ub_gather.hip, tables of 1-8
-// GB); the element-by-element gather above reaches 23 G. Here the wavefront's 64 lists — one contiguous piece of the
-// output — are put together in LDS: in step j of a round, group g fetches one aligned 128-byte line of the list of its
+// result list i = d_tmp[src[i] .. src[i] + (offsets[i + 1] - offsets[i])), written to d_hits[offsets[i] ..), a line at a
+// time. Random 128-byte lines come out of HBM at 45-50 G per second when a group of eight lanes asks for one
+// (tools/ub_gather.hip, tables of 1-8 GB); an element-by-element gather reaches 23 G. Here the wavefront's 64 lists — one
+// contiguous piece of the output — are put together in LDS: in step j of a round, group g fetches one aligned 128-byte line of the list of its
 // lane j (lane p the p-th 16 bytes) and every lane drops the up to four ids of its 16 bytes that belong to the list at
 // their places in the piece; the eight steps' loads leave together, a list of k lines takes k rounds. The piece then
 // leaves in whole lines. Pieces beyond the buffer go in runs of consecutive lists that fit.
@@ -2251,7 +1939,7 @@ __global__ __launch_bounds__(kQThreads) void k_permute_lines(uint64_t *__restric
   const uint64_t we = __shfl((unsigned long long)o1, kWave - 1, kWave);
   const uint64_t sp = i < n && o1 > o0 ? word & kSelfPosMask : 0ull;
   if (we - wb > 0xFFFFFFFFull || __any(o1 - o0 > kPermListMax)) {
-    // (rare: the element-wise gather of k_permute_lists, one list per lane)
+    // (rare: an element-wise gather, one list per lane)
     if (i < n)
       for (uint64_t k = 0; k < o1 - o0; ++k)
         if (o0 + k < cap && sp + k < cap) hits[o0 + k] = tmp[sp + k];
@@ -2342,27 +2030,26 @@ __global__ __launch_bounds__(kQThreads) void k_permute_lines(uint64_t *__restric
   }
 }
 
+// The index overlapped with itself (bivx_self_overlaps_dev): the queries are the index's own intervals in SLOT order —
+// position-sorted by construction, which is what k_query_pipe_dense is for — and the result is wanted in id order:
+// perm = the slots' ids. The kernel writes the lists back to back in slot order into d_tmp_hits and leaves, per id, the
+// list's length and where it begins; k_permute_lines makes the offsets and gathers the lists into place.
+// (Writing every list straight to its place from the slot-order pass was tried first: 50 M lists of ~68 bytes at random
+// places of a 3.4 GB buffer are partial-line writes the memory side has to read-modify-write: 6.1 ms for that pass at
+// config 5. Random READS of the same lists run at the gather rate, and the writes are a stream.)
 int launch_self_overlaps(const IndexView &v, const uint32_t *d_qchrom, const uint32_t *d_qlow, const uint32_t *d_qhigh,
                          const uint32_t *d_perm, size_t n, uint64_t *d_src_by_id,
                          uint64_t *d_offsets_scratch, uint32_t *d_tmp_hits, uint64_t cap, uint64_t *ws, bool self_clean,
-                         hipStream_t s) {
+                         const RouteKnobs &knobs, hipStream_t s) {
   const int flags = (self_clean ? kFlagSelfClean : 0) | kFlagFinal | kFlagSorted;
-  unsigned wgs = 512;
-  {
-    wgs = 2u * cus_of_current_device();
-    if (const char *e = std::getenv("BIVX_PIPE_WGS")) {
-      const long w = std::atol(e);
-      if (w >= 1 && w <= 65536) wgs = (unsigned)w;
-    }
-  }
-  if (n > pipe_queries_per_launch()) {  // (launches would have to chain their output positions: not needed below 62 M)
-    set_error("bivx_self_overlaps_dev: more than %zu intervals", pipe_queries_per_launch());
+  if (n > (size_t)kFMaxTiles * kPTile) {  // (launches would have to chain their output positions: not needed below 62 M)
+    set_error("bivx_self_overlaps_dev: more than %zu intervals", (size_t)kFMaxTiles * kPTile);
     return BIVX_E_RANGE;
   }
   const unsigned tiles = (unsigned)((n + kPTile - 1) / kPTile);
   PipeArgs a{d_qchrom, d_qlow, d_qhigh, 0, n, d_offsets_scratch, d_tmp_hits, cap, ws, tiles, flags, 1u,
              nullptr, nullptr, d_perm, d_src_by_id, nullptr, 0u, kPTile};
-  hipLaunchKernelGGL(k_query_pipe_dense, dim3(tiles < wgs ? tiles : wgs), dim3(kPThreads), 0, s, v, a);
+  hipLaunchKernelGGL(k_query_pipe_dense, pipe_grid(tiles, knobs), dim3(kPThreads), 0, s, v, a);
   if (cap != 0) {
     a.seq = 0;  // (k_fill_slices: index order)
     hipLaunchKernelGGL(k_fill_slices<false>, dim3(kFillBlocks), dim3(kQThreads), 0, s, v, a);
@@ -2375,18 +2062,7 @@ int launch_self_overlaps(const IndexView &v, const uint32_t *d_qchrom, const uin
 int launch_permute_lists(uint64_t *d_offsets, const uint64_t *d_src, const uint32_t *d_tmp, uint32_t *d_hits, size_t n,
                          uint64_t cap, bool sort_ids, bool *sorted, void *d_scan, hipStream_t s) {
   *sorted = false;
-  static const bool by_elements = [] {  // (BIVX_PERMUTE=elements: the first form, for comparison)
-    const char *e = std::getenv("BIVX_PERMUTE");
-    return e && e[0] == 'e';
-  }();
-  if (n == 0 || by_elements) {
-    BIVX_TRY(exclusive_scan_lengths_u64(d_src, d_offsets, n, d_scan, s));
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_permute_lists, dim3((unsigned)((n + kQThreads - 1) / kQThreads)), dim3(kQThreads), 0, s, d_offsets,
-                       d_src, d_tmp, d_hits, n, cap);
-    BIVX_HIP(hipGetLastError());
-    return 0;
-  }
+  if (n == 0) return exclusive_scan_lengths_u64(d_src, d_offsets, n, d_scan, s);
   const uint64_t *tile_prefix = nullptr, *block_sums = nullptr;
   BIVX_TRY(self_length_sums(d_src, n, d_scan, &tile_prefix, &block_sums, s));
   if (sort_ids) {

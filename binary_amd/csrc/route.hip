@@ -137,9 +137,9 @@ __global__ __launch_bounds__(256) void k_rows_to_queries(const uint64_t *__restr
 
 // query i's list: src_hits[qsrc[i] ..) of qoff[i + 1] - qoff[i] ids, to hits[qoff[i] ..). A wavefront takes 64 consecutive
 // queries — one contiguous piece of the output — and every lane one output element at a time: the element's list is found
-// by bisection of the 64 list ends in LDS, its source is a gather, the stores are a stream (the way of k_permute_lists,
-// query_pipe.hip: a list of thousands of ids keeps all 64 lanes busy, 64 lists of three ids take one trip). Every element
-// stored is one that was loaded; nothing else is written.
+// by bisection of the 64 list ends in LDS, its source is a gather, the stores are a stream (a list of thousands of ids keeps
+// all 64 lanes busy, 64 lists of three ids take one trip). Every element stored is one that was loaded; nothing else is
+// written.
 __global__ __launch_bounds__(256) void k_batch_lists(const uint64_t *__restrict__ qoff, const uint64_t *__restrict__ qsrc,
                                                      const uint32_t *__restrict__ src_hits, uint32_t *__restrict__ hits,
                                                      size_t n) {

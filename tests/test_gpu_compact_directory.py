@@ -132,7 +132,7 @@ def test_pipe_csr_equals_the_table_route_on_a_hotspot_index():
     low, high, chrom = _uniform_plus_hotspot(400_000, 3000)
     g = synth.gen_genome(1000, 200_000, 1000)
     rng = np.random.default_rng(7)
-    hq = 100  # queries over the hotspot: windows through escaped groups (few: pipe_eligible wants <= 6 ids per query)
+    hq = 100  # queries over the hotspot: windows through escaped groups (few: k_query_pipe wants <= 6 ids per query)
     hlo = (999_000 + 1_234_567 * rng.integers(0, 10, hq) + rng.integers(0, 3000, hq)).astype(np.uint32)
     qlo = np.concatenate([g["qlow"], hlo])
     qhi = np.concatenate([g["qhigh"], hlo + rng.integers(0, 100, hq).astype(np.uint32)])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the batch-size threshold of pipe_eligible belongs: config 2's index (1 M intervals on chr1), point queries in
+"""Where the batch-size threshold of k_query_pipe (query_route.h) belongs: config 2's index (1 M intervals on chr1), point queries in
 generation order, batches of 0.125 M .. 2 M queries through k_query_fused (BIVX_PIPE=0) and through k_query_pipe
 (BIVX_PIPE=2). Diagnostic; one line per size."""
 import os

@@ -2,6 +2,7 @@
 # Builds binary_amd/libbivx.so.<tag> with extra compiler flags for the listed translation units (the others come from the
 # normal build), for A/B runs on the GPU box without compiling there: BIVX_LIB=binary_amd/libbivx.so.<tag> python ...
 # usage: tools/build_variant.sh <tag> "<extra flags>" [unit ...]      (units default to query_pipe)
+# (BIVX_FUSED_THREADS and BIVX_PIPE_THREADS also size the launches planned in query_route.h: list every unit for them)
 set -eo pipefail
 TAG=$1; EXTRA=$2; shift; shift
 UNITS=${*:-query_pipe}

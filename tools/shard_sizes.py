@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a rank of `bench.py --gpus N` runs (config 4: config 3's set, chromosomes LPT-assigned), timed on ONE GPU for
 N = 2, 4, 8 with the pipelined kernel forced (BIVX_PIPE=2) and off (BIVX_PIPE=0): where the batch-size threshold of
-pipe_eligible belongs. Diagnostic; prints one line per (N, kernel)."""
+k_query_pipe (query_route.h) belongs. Diagnostic; prints one line per (N, kernel)."""
 import os
 import sys
 
